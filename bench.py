@@ -39,8 +39,8 @@ from bench_common import (BYTES_OUT_P, BYTES_OUT_PV, ELEM_BYTES_PER_SAT, FLOPS_P
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 200; 20 with --config5-share)")
+    ap.add_argument("--warmup", type=int, default=None, help="warm-up steps (default 100; 5 with --config5-share)")
     ap.add_argument("--precondition-ms", type=float, default=200.0,
                     help="run the step back to back for this long before the W warm-up steps (device clocks "
                          "reach their sustained level ~30 ms after load onset; 0 disables)")
@@ -88,14 +88,51 @@ def parse_args():
     ap.add_argument("--secondary-skip", default="", help="comma-separated keys of secondary workloads to skip (e.g. config5_share)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=5.0)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (a fixed, seeded sample "
+                         "of satellites when the arrays exceed %d MB; the rows taken in sat_index.npy)" % (DUMP_BUDGET // 10 ** 6))
+    a = ap.parse_args()
+    if a.steps is not None and a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup is not None and a.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return a
+
+
+DUMP_BUDGET = 64 * 10 ** 6     # --dump-outputs: bytes of all files together (headers included)
+
+
+def dump_outputs(out_dir, arrays, sat_axis, n_sats, seed=20261015):
+    """--dump-outputs: `arrays` = [(name, device tensor)] as the timed path left them, satellites along `sat_axis` (n_sats
+    of them).  Everything is written if it fits the budget; otherwise the same seeded sample of satellites (all times) is
+    taken from every array -- identical on every run with the same arguments.  Returns {file: shape}."""
+    import torch
+    per_sat = sum(t.numel() // n_sats * t.element_size() for _, t in arrays)
+    room = DUMP_BUDGET - 8 * n_sats - 4096 * (len(arrays) + 1)     # (the row list and the .npy headers)
+    k = min(n_sats, max(1, room // max(1, per_sat)))
+    if k * per_sat > room:
+        raise SystemExit("bench.py --dump-outputs: one satellite's outputs alone exceed %d MB" % (DUMP_BUDGET // 10 ** 6))
+    rows = np.arange(n_sats) if k == n_sats else np.sort(np.random.default_rng(seed).choice(n_sats, k, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, t in arrays:
+        idx = torch.as_tensor(rows, dtype=torch.int64, device=t.device)
+        h = t.index_select(sat_axis, idx).cpu().numpy()
+        assert h.dtype in (np.float32, np.float64), h.dtype
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(h))
+        written[name + ".npy"] = list(h.shape)
+    np.save(os.path.join(out_dir, "sat_index.npy"), rows.astype(np.float64))
+    written["sat_index.npy"] = [int(k)]
+    return written
 
 def main():
     a = parse_args()
     if a.config5_share:
         a.sats, a.times, a.f32_out, a.deep = 125000, 10000, True, 0
-        if a.steps == 200 and a.warmup == 100:
-            a.steps, a.warmup = 20, 5
+    if a.steps is None:
+        a.steps = 20 if a.config5_share else 200
+    if a.warmup is None:
+        a.warmup = 5 if a.config5_share else 100
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -264,6 +301,23 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed, ev_ms = float(tt[0]), float(tt[1])
 
+    # --dump-outputs: the arrays of the last timed step, taken before anything below launches into the same buffers (rank 0:
+    # the gathered catalog-ordered arrays when the step gathers, else its own satellites)
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        if sharded and gather:
+            res, n_dump = sp.results(), n_total
+        elif sharded:
+            rows_, res = sp.local_results()
+            n_dump = len(rows_)
+        else:
+            res = [t[:, :n_local] if layout == _native.TIME_MAJOR else t for t in ([pos, vel] if vel_on else [pos])]
+            n_dump = n_local
+        names = ["positions", "velocities"][:len(res)]
+        sat_axis = 1 if (not sharded and layout == _native.TIME_MAJOR) else 0
+        dumped = {"dir": a.dump_outputs, "sat_axis": sat_axis,
+                  "files": dump_outputs(a.dump_outputs, list(zip(names, res)), sat_axis, n_dump)}
+
     # config 4 extras, timed the same way (barrier, events, max over ranks): the kernels alone -- eager and as hipGraphs -- and
     # the "replicate" point (every GPU propagates the FULL catalog itself): bench_sharded.py
     kernel_only_ms = kernel_graphs_ms = replicate_ms = None
@@ -390,6 +444,7 @@ def main():
         },
         "power": power,
         "valu_issue": valu_issue,
+        "dump_outputs": dumped,
         "fp64_valu": {
             "achieved": tflops, "peak": FP64_VALU_PEAK_TF, "unit": "TFLOP/s",
             "flops_per_propagation": FLOPS_PER_PROP,
