@@ -70,10 +70,19 @@ const char *const kFieldNames[] = {
 #undef X
 };
 
+// Owners of device and pinned-host resources: move-only, each frees what it holds in its destructor.  Statics that hold one
+// are heap-allocated and never destroyed (at process exit the HIP runtime may already be gone).
+
+// grow-only device buffer of at least 64 elements
 template <class T>
 struct DevBuf {
     T *p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept { swap(o); }
+    DevBuf &operator=(DevBuf &&o) noexcept { swap(o); return *this; }
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    void swap(DevBuf &o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); }
     int ensure(size_t n)
     {
         if (n <= cap) return AZ_OK;
@@ -85,40 +94,81 @@ struct DevBuf {
         cap = want;
         return AZ_OK;
     }
-    void release()
+};
+
+// grow-only pinned host buffer: `cap` bytes, a power of two from 64 KB
+struct PinnedBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    PinnedBuf() = default;
+    PinnedBuf(PinnedBuf &&o) noexcept { swap(o); }
+    PinnedBuf &operator=(PinnedBuf &&o) noexcept { swap(o); return *this; }
+    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+    void swap(PinnedBuf &o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); }
+    int32_t ensure(size_t bytes)
     {
-        if (p) (void)hipFree(p);
+        if (bytes <= cap) return AZ_OK;
+        size_t want = std::max<size_t>(cap, 65536);
+        while (want < bytes) want *= 2;
+        if (p) (void)hipHostFree(p);
         p = nullptr;
         cap = 0;
+        if (!hip_ok(hipHostMalloc(&p, want, hipHostMallocDefault), "hipHostMalloc")) return AZ_ERR_HIP;
+        cap = want;
+        return AZ_OK;
     }
 };
 
-// pinned staging slots of the host-returning calls (copy_back_staged)
+// a HIP stream or event: created here and destroyed with the owner, or borrowed (never destroyed by it) -- the device's shared
+// stream of small handles, or a handle's side stream that IS its launch stream
+template <class H, hipError_t (*Create)(H *, unsigned), hipError_t (*Destroy)(H)>
+class HipHandle {
+  public:
+    HipHandle() = default;
+    HipHandle(HipHandle &&o) noexcept { swap(o); }
+    HipHandle &operator=(HipHandle &&o) noexcept { swap(o); return *this; }
+    ~HipHandle() { reset(); }
+    void swap(HipHandle &o) noexcept { std::swap(h_, o.h_); std::swap(own_, o.own_); }
+    hipError_t create(unsigned flags)
+    {
+        reset();
+        own_ = true;
+        return Create(&h_, flags);
+    }
+    void borrow(H h)
+    {
+        reset();
+        h_ = h;
+        own_ = false;
+    }
+    void reset()
+    {
+        if (h_ && own_) (void)Destroy(h_);
+        h_ = nullptr;
+    }
+    bool owned() const { return h_ && own_; }
+    operator H() const { return h_; }
+
+  private:
+    H h_ = nullptr;
+    bool own_ = false;
+};
+using Stream = HipHandle<hipStream_t, hipStreamCreateWithFlags, hipStreamDestroy>;
+using Event = HipHandle<hipEvent_t, hipEventCreateWithFlags, hipEventDestroy>;
+
+// pinned staging slots of the host-returning calls (copy_back_staged), allocated on first use
 constexpr int kStageSlots = 3;
 constexpr size_t kStageChunk = size_t(16) << 20;
 struct HostStager {
-    void *slot[kStageSlots] = {nullptr, nullptr, nullptr};
-    hipEvent_t ev[kStageSlots] = {nullptr, nullptr, nullptr};
-    bool ready = false;
+    Event ev[kStageSlots];
+    PinnedBuf slot[kStageSlots];
     int32_t ensure()
     {
-        if (ready) return AZ_OK;
         for (int k = 0; k < kStageSlots; ++k) {
-            if (!slot[k] && !hip_ok(hipHostMalloc(&slot[k], kStageChunk, hipHostMallocDefault), "hipHostMalloc(stage)")) return AZ_ERR_HIP;
-            if (!ev[k] && !hip_ok(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming), "hipEventCreate")) return AZ_ERR_HIP;
+            if (slot[k].ensure(kStageChunk) != AZ_OK) return AZ_ERR_HIP;
+            if (!ev[k] && !hip_ok(ev[k].create(hipEventDisableTiming), "hipEventCreate")) return AZ_ERR_HIP;
         }
-        ready = true;
         return AZ_OK;
-    }
-    void release()
-    {
-        for (int k = 0; k < kStageSlots; ++k) {
-            if (slot[k]) (void)hipHostFree(slot[k]);
-            if (ev[k]) (void)hipEventDestroy(ev[k]);
-            slot[k] = nullptr;
-            ev[k] = nullptr;
-        }
-        ready = false;
     }
 };
 } // namespace
@@ -127,8 +177,16 @@ struct azh_constellation {
     int device = 0;
     size_t n = 0, n_pad = 0;
     AzGrav g{};
-    double *d_el = nullptr;
-    unsigned *d_flags = nullptr;
+    // the streams and events come first: members are released in reverse order, so every buffer below goes before them
+    Stream s_main, s_deep, s_ecc; // s_main: borrowed for a handle of a few satellites (the device's shared stream, small_stream),
+                                  // whose side streams then borrow s_main
+    Event ev_fork, ev_join, ev_fork2, ev_join2, ev_t0, ev_t1;
+    Event ev_one;   // recorded behind the kernels of the most recent k_one_fast call (azh_last_one_stats waits on it:
+                    // the caller's stream may be gone by then)
+    Event ev_graph; // recorded behind every hipGraphLaunch (drop_graphs waits on it, for the same reason; own streams only).  It
+                    // orders nothing but the destruction of graphs: no system-scope fence (measured: +3.5 us per replay, +6 with it)
+    DevBuf<double> d_el;
+    DevBuf<unsigned> d_flags;
     std::vector<unsigned> h_flags;
     std::vector<double> h_epoch;
     std::vector<double> h_raw[AZ_NUM_RAW]; // the TLE-unit inputs (for azh_constellation_subset)
@@ -172,18 +230,14 @@ struct azh_constellation {
     DevBuf<unsigned char> d_one_e;
     DevBuf<unsigned> d_one_items; // k_one_fast -> k_one_satellite hand-over list (count, then segment indices)
     unsigned one_segments = 0;     // segments of the most recent one-satellite call that k_one_fast was launched on (azh_last_one_stats)
-    hipEvent_t ev_one = nullptr;   // recorded behind the kernels of the most recent k_one_fast call (azh_last_one_stats waits on it:
-                                   // the caller's stream may be gone by then)
-    void *h_stage = nullptr; // pinned host staging for small one-satellite calls: h_stage_cap points (grows to kOneStage)
-    size_t h_stage_cap = 0;
+    PinnedBuf h_stage; // pinned host staging for small one-satellite calls: kOnePointBytes per point (grows to kOneStage points)
     // the inputs of the staged grid (stage_inputs skips the staging of byte-identical ones)
     std::vector<double> h_times, h_offsets;
     std::vector<uint8_t> h_mask;
     double staged_ref_jd = 0.0;
     hipStream_t staged_stream = nullptr;
     bool staged_valid = false;
-    void *h_small = nullptr; // pinned host buffer the kernels of a SMALL host-returning constellation call write into directly
-    size_t h_small_cap = 0;
+    PinnedBuf h_small;       // pinned host buffer the kernels of a SMALL host-returning constellation call write into directly
     HostStager stager;       // pinned staging slots of the host-returning calls (copy_back_staged), allocated on first use
     bool seeds_valid = false; // resonance seeds match the staged times/offsets and tile
     unsigned seeds_tile = 0;
@@ -194,9 +248,6 @@ struct azh_constellation {
     bool have_offsets = false, have_mask = false;
     unsigned cached_n_times = 0;
     int cached_mode = 0;
-    hipStream_t s_main = nullptr, s_deep = nullptr, s_ecc = nullptr;
-    bool own_stream = true; // false: s_main is the device's shared stream of small handles (never destroyed with the handle)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_fork2 = nullptr, ev_join2 = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
     unsigned off_cat = 0; // d_list + off_cat: near-earth members in plain catalog order (k_tiles_fast: runs of consecutive rows)
     unsigned off_deep_cat = 0; // d_list + off_deep_cat: deep-space members in plain catalog order (lane = time kernels)
     unsigned off_rowmap = 0;   // d_list + off_rowmap: per catalog row, kind << 30 | slot (AZ_ROW_*: k_tiles_fast)
@@ -238,6 +289,7 @@ struct azh_constellation {
     std::vector<double> h_el;                            // [AZ_NUM_FIELDS][n_pad] or empty
     std::vector<std::pair<size_t, std::vector<double>>> h_cols; // (satellite, AZ_NUM_FIELDS contiguous doubles)
     size_t h_cols_next = 0;
+    ~azh_constellation(); // (sets the device and drops the graph cache; the members then release themselves)
 };
 
 namespace {
@@ -276,54 +328,6 @@ hipStream_t small_stream(int device)
 }
 
 void drop_graphs(azh_constellation *c);
-void destroy(azh_constellation *c)
-{
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    drop_graphs(c);
-    if (c->d_el) (void)hipFree(c->d_el);
-    if (c->d_flags) (void)hipFree(c->d_flags);
-    c->d_list.release();
-    c->d_times.release();
-    c->d_offsets.release();
-    c->d_sin.release();
-    c->d_cos.release();
-    c->d_seeds.release();
-    c->d_node_cache.release();
-    c->d_deep_tmp.release();
-    c->d_inc.release();
-    c->d_fast_rec.release();
-    c->d_delta.release();
-    c->d_delta64.release();
-    for (auto &pl : c->plan) { pl.win.release(); pl.flag.release(); pl.redo.release(); }
-    c->d_tgt.release();
-    c->d_part_d2.release();
-    c->d_out_d.release();
-    c->d_part_t.release();
-    c->d_out_t.release();
-    c->d_one_t.release();
-    c->d_one_o.release();
-    c->d_one_e.release();
-    c->d_one_items.release();
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
-    if (c->h_small) (void)hipHostFree(c->h_small);
-    c->stager.release();
-    c->d_mask.release();
-    c->d_host_pos.release();
-    c->d_host_vel.release();
-    c->d_host_err.release();
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    if (c->ev_fork2) (void)hipEventDestroy(c->ev_fork2);
-    if (c->ev_join2) (void)hipEventDestroy(c->ev_join2);
-    if (c->ev_one) (void)hipEventDestroy(c->ev_one);
-    if (c->s_ecc && c->s_ecc != c->s_main) (void)hipStreamDestroy(c->s_ecc);
-    if (c->ev_t0) (void)hipEventDestroy(c->ev_t0);
-    if (c->ev_t1) (void)hipEventDestroy(c->ev_t1);
-    if (c->s_deep && c->s_deep != c->s_main) (void)hipStreamDestroy(c->s_deep);
-    if (c->s_main && c->own_stream) (void)hipStreamDestroy(c->s_main);
-    delete c;
-}
 
 // raw columns (AzRawField order, each of length n) -> device table via the init kernel
 int32_t build(const std::vector<double> (&cols)[AZ_NUM_RAW], size_t n, int grav, int device, azh_constellation **out)
@@ -338,167 +342,145 @@ int32_t build(const std::vector<double> (&cols)[AZ_NUM_RAW], size_t n, int grav,
         g_last_error = "no such HIP device";
         return AZ_ERR_HIP;
     }
-    azh_constellation *c = new (std::nothrow) azh_constellation();
+    std::unique_ptr<azh_constellation> c(new (std::nothrow) azh_constellation());
     if (!c) return AZ_ERR_ALLOC_FAILED;
     c->device = device;
     c->n = n;
     c->n_pad = (n + 63) / 64 * 64;
     c->g = make_grav(grav);
-    int32_t rc = AZ_OK;
-    double *d_raw = nullptr;
-    do {
-        if (set_device(c) != AZ_OK) { rc = AZ_ERR_HIP; break; }
-        // one launch stream + two side streams (deep-space launch; eccentric launch and redo pass beside the bulk).  A handle of
-        // a few satellites -- what sgp4_init / Satrec create, possibly by the thousand -- has nothing to overlap: its side
-        // streams ARE the launch stream (the fork / join events then order a stream with itself)
-        const bool side_streams = n > 16;
-        if (!side_streams) {
-            c->s_main = small_stream(device);
-            c->own_stream = false;
-        }
-        if ((side_streams ? !hip_ok(hipStreamCreateWithFlags(&c->s_main, hipStreamNonBlocking), "hipStreamCreate") : c->s_main == nullptr) ||
-            (side_streams && (!hip_ok(hipStreamCreateWithFlags(&c->s_deep, hipStreamNonBlocking), "hipStreamCreate") ||
-                              !hip_ok(hipStreamCreateWithFlags(&c->s_ecc, hipStreamNonBlocking), "hipStreamCreate"))) ||
-            !hip_ok(hipEventCreateWithFlags(&c->ev_fork2, hipEventDisableTiming), "hipEventCreate") ||
-            !hip_ok(hipEventCreateWithFlags(&c->ev_join2, hipEventDisableTiming), "hipEventCreate") ||
-            !hip_ok(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming), "hipEventCreate") ||
-            !hip_ok(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming), "hipEventCreate") ||
-            !hip_ok(hipEventCreateWithFlags(&c->ev_one, hipEventDisableTiming), "hipEventCreate") ||
-            !hip_ok(hipEventCreate(&c->ev_t0), "hipEventCreate") || !hip_ok(hipEventCreate(&c->ev_t1), "hipEventCreate")) {
-            rc = AZ_ERR_HIP;
-            break;
-        }
-        if (!side_streams) c->s_deep = c->s_ecc = c->s_main;
-        const size_t np = c->n_pad;
-        if (!hip_ok(hipMalloc((void **)&c->d_el, sizeof(double) * AZ_NUM_FIELDS * np), "hipMalloc(el)") ||
-            !hip_ok(hipMalloc((void **)&c->d_flags, sizeof(unsigned) * np), "hipMalloc(flags)") ||
-            !hip_ok(hipMalloc((void **)&d_raw, sizeof(double) * AZ_NUM_RAW * np), "hipMalloc(raw)")) {
-            rc = AZ_ERR_HIP;
-            break;
-        }
-        std::vector<double> staging((size_t)AZ_NUM_RAW * np, 0.0);
-        for (int k = 0; k < AZ_NUM_RAW; ++k) memcpy(&staging[(size_t)k * np], cols[k].data(), sizeof(double) * n);
-        if (!hip_ok(hipMemcpyAsync(d_raw, staging.data(), sizeof(double) * staging.size(), hipMemcpyHostToDevice, c->s_main), "H2D raw") ||
-            !hip_ok(hipMemsetAsync(c->d_el, 0, sizeof(double) * AZ_NUM_FIELDS * np, c->s_main), "memset el") ||
-            !hip_ok(hipMemsetAsync(c->d_flags, 0, sizeof(unsigned) * np, c->s_main), "memset flags")) {
-            rc = AZ_ERR_HIP;
-            break;
-        }
-        hipLaunchKernelGGL(k_init, dim3((unsigned)(np / 64)), dim3(64), 0, c->s_main, d_raw, n, np, c->g, c->d_el, c->d_flags);
-        if (!hip_ok(hipGetLastError(), "k_init launch")) { rc = AZ_ERR_HIP; break; }
-        c->h_flags.resize(n);
-        if (np <= kHostMirrorPad) { // (host route of few-point calls: the initialised columns travel back with the status words)
-            c->h_el.resize((size_t)AZ_NUM_FIELDS * np);
-            if (!hip_ok(hipMemcpyAsync(c->h_el.data(), c->d_el, sizeof(double) * c->h_el.size(), hipMemcpyDeviceToHost, c->s_main), "D2H el")) {
-                rc = AZ_ERR_HIP;
-                break;
-            }
-        }
-        if (!hip_ok(hipMemcpyAsync(c->h_flags.data(), c->d_flags, sizeof(unsigned) * n, hipMemcpyDeviceToHost, c->s_main), "D2H flags") ||
-            !hip_ok(hipStreamSynchronize(c->s_main), "sync(init)")) {
-            rc = AZ_ERR_HIP;
-            break;
-        }
-        c->h_epoch = cols[R_epoch_jd];
-        for (int k = 0; k < AZ_NUM_RAW; ++k) c->h_raw[k] = cols[k];
-        // launch lists.
-        //  [near-earth]  catalog order, except that inside every group of AZ_BLOCK consecutive
-        //      members (= one workgroup = 4 waves) the members are ordered by eccentricity class.
-        //      A single e = 0.2 satellite needs ~4 Kepler-Newton trips and the wide rotation tier and
-        //      would drag the 63 other lanes of its wave along (4% such members touch 93% of the
-        //      waves of an unsorted catalog); after the in-group ordering they share the group's last
-        //      wave.  The group still writes the same contiguous span of rows.
-        //  [deep-space by resonance class]  uniform integrator branch per wave.
-        //  [failed inits]
-        std::vector<unsigned> list;
-        list.reserve(n);
-        for (size_t s = 0; s < n; ++s)
-            if (AZ_FLAG_ERR(c->h_flags[s]) == 0 && !(c->h_flags[s] & AZ_FLAG_DEEP)) list.push_back((unsigned)s);
-        c->n_sgp4 = (unsigned)list.size();
-        for (size_t g0 = 0; g0 < list.size(); g0 += AZ_BLOCK) {
-            const size_t g1 = std::min(g0 + (size_t)AZ_BLOCK, list.size());
-            std::stable_sort(list.begin() + g0, list.begin() + g1, [&](unsigned x, unsigned y) {
-                return AZ_FLAG_ECLASS(c->h_flags[x]) < AZ_FLAG_ECLASS(c->h_flags[y]);
-            });
-        }
-        {
-            // deep space: order by (resonance class, near-equatorial [Lyddane branch], eccentricity
-            // class) so that the integrator branch, the Lyddane branch and the number of Kepler-Newton
-            // trips are as uniform as possible inside each wave
-            std::vector<unsigned> deep;
-            for (size_t s = 0; s < n; ++s)
-                if (AZ_FLAG_ERR(c->h_flags[s]) == 0 && (c->h_flags[s] & AZ_FLAG_DEEP)) deep.push_back((unsigned)s);
-            const std::vector<double> &incl = cols[R_incl_deg];
-            auto key = [&](unsigned s) {
-                const unsigned f = c->h_flags[s];
-                const unsigned low = incl[s] < 12.5 ? 1u : 0u; // 0.2 rad = 11.46 deg, with margin for the periodics
-                return (AZ_FLAG_IREZ(f) << 4) | (low << 2) | AZ_FLAG_ECLASS(f);
-            };
-            std::stable_sort(deep.begin(), deep.end(), [&](unsigned x, unsigned y) { return key(x) < key(y); });
-            list.insert(list.end(), deep.begin(), deep.end());
-        }
-        c->n_sdp4 = (unsigned)list.size() - c->n_sgp4;
-        for (size_t s = 0; s < n; ++s)
-            if (AZ_FLAG_ERR(c->h_flags[s]) != 0) list.push_back((unsigned)s);
-        c->n_bad = (unsigned)list.size() - c->n_sgp4 - c->n_sdp4;
-        // the near-earth members once more, in catalog order, by eccentricity class: [class 0 | other classes]
-        // (the two instantiations of k_rows_fast)
-        c->off_circ = (unsigned)list.size();
-        for (size_t s = 0; s < n; ++s)
-            if (AZ_FLAG_ERR(c->h_flags[s]) == 0 && !(c->h_flags[s] & AZ_FLAG_DEEP) && AZ_FLAG_ECLASS(c->h_flags[s]) == 0)
-                list.push_back((unsigned)s);
-        c->n_circ = (unsigned)list.size() - c->off_circ;
-        for (size_t s = 0; s < n; ++s)
-            if (AZ_FLAG_ERR(c->h_flags[s]) == 0 && !(c->h_flags[s] & AZ_FLAG_DEEP) && AZ_FLAG_ECLASS(c->h_flags[s]) != 0)
-                list.push_back((unsigned)s);
-        // ... and once in plain catalog order (time-major tiles of 16 consecutive rows, k_tiles_fast)
-        c->off_cat = (unsigned)list.size();
-        for (size_t s = 0; s < n; ++s)
-            if (AZ_FLAG_ERR(c->h_flags[s]) == 0 && !(c->h_flags[s] & AZ_FLAG_DEEP)) list.push_back((unsigned)s);
-        // ... and the deep-space members in plain catalog order: one wave per satellite needs no grouping by branch, and
-        // runs of consecutive rows leave the time-major transposer as single long stores
-        c->off_deep_cat = (unsigned)list.size();
-        for (size_t s = 0; s < n; ++s)
-            if (AZ_FLAG_ERR(c->h_flags[s]) == 0 && (c->h_flags[s] & AZ_FLAG_DEEP)) list.push_back((unsigned)s);
-        // ... and the row map of the time-major tile kernel: what every catalog row is and where its data comes from
-        c->off_rowmap = (unsigned)list.size();
-        {
-            unsigned near = 0, deepn = 0;
-            for (size_t s = 0; s < n; ++s) {
-                const unsigned f = c->h_flags[s];
-                if (AZ_FLAG_ERR(f) != 0) list.push_back((unsigned)AZ_ROW_ZERO << 30);
-                else if (f & AZ_FLAG_DEEP) list.push_back(((unsigned)AZ_ROW_COPY << 30) | deepn++);
-                else list.push_back(((unsigned)AZ_ROW_NEAR << 30) | near++);
-            }
-        }
-        // ... and once more for the lane = satellite time-major kernel, whose plan and redo items count near-earth slots in
-        // the [class 0 | other classes] list: slot < n_circ = computed there, the rest arrive through the scratch array
-        c->off_rowmap2 = (unsigned)list.size();
-        {
-            unsigned circ = 0, eccn = 0, deepn = 0;
-            for (size_t s = 0; s < n; ++s) {
-                const unsigned f = c->h_flags[s];
-                if (AZ_FLAG_ERR(f) != 0) list.push_back((unsigned)AZ_ROW_ZERO << 30);
-                else if (f & AZ_FLAG_DEEP) list.push_back(((unsigned)AZ_ROW_COPY << 30) | deepn++);
-                else if (AZ_FLAG_ECLASS(f) == 0) list.push_back(((unsigned)AZ_ROW_NEAR << 30) | circ++);
-                else list.push_back(((unsigned)AZ_ROW_NEAR << 30) | (c->n_circ + eccn++));
-            }
-        }
-        if (const char *e = getenv("ASTROZ_AMD_COLS")) c->cols_kernel = atoi(e);
-        if (const char *e = getenv("ASTROZ_AMD_GRAPHS")) c->graphs_on = atoi(e);
-        c->h_list = list;
-        if (c->d_list.ensure(list.size()) != AZ_OK ||
-            !hip_ok(hipMemcpy(c->d_list.p, list.data(), sizeof(unsigned) * list.size(), hipMemcpyHostToDevice), "H2D list")) {
-            rc = AZ_ERR_HIP;
-            break;
-        }
-    } while (0);
-    if (d_raw) (void)hipFree(d_raw);
-    if (rc != AZ_OK) {
-        destroy(c);
-        return rc;
+    if (set_device(c.get()) != AZ_OK) return AZ_ERR_HIP;
+    // one launch stream + two side streams (deep-space launch; eccentric launch and redo pass beside the bulk).  A handle of
+    // a few satellites -- what sgp4_init / Satrec create, possibly by the thousand -- has nothing to overlap: its side
+    // streams ARE the launch stream (the fork / join events then order a stream with itself), and it captures no graphs
+    if (n > 16) {
+        if (!hip_ok(c->s_main.create(hipStreamNonBlocking), "hipStreamCreate") ||
+            !hip_ok(c->s_deep.create(hipStreamNonBlocking), "hipStreamCreate") ||
+            !hip_ok(c->s_ecc.create(hipStreamNonBlocking), "hipStreamCreate") ||
+            !hip_ok(c->ev_graph.create(hipEventDisableTiming | hipEventDisableSystemFence), "hipEventCreate"))
+            return AZ_ERR_HIP;
+    } else {
+        c->s_main.borrow(small_stream(device));
+        if (!c->s_main) return AZ_ERR_HIP;
+        c->s_deep.borrow(c->s_main);
+        c->s_ecc.borrow(c->s_main);
     }
-    *out = c;
+    for (Event *e : {&c->ev_fork2, &c->ev_join2, &c->ev_fork, &c->ev_join, &c->ev_one})
+        if (!hip_ok(e->create(hipEventDisableTiming), "hipEventCreate")) return AZ_ERR_HIP;
+    if (!hip_ok(c->ev_t0.create(hipEventDefault), "hipEventCreate") || !hip_ok(c->ev_t1.create(hipEventDefault), "hipEventCreate"))
+        return AZ_ERR_HIP;
+    const size_t np = c->n_pad;
+    DevBuf<double> d_raw;
+    if (c->d_el.ensure((size_t)AZ_NUM_FIELDS * np) != AZ_OK || c->d_flags.ensure(np) != AZ_OK || d_raw.ensure((size_t)AZ_NUM_RAW * np) != AZ_OK)
+        return AZ_ERR_HIP;
+    std::vector<double> staging((size_t)AZ_NUM_RAW * np, 0.0);
+    for (int k = 0; k < AZ_NUM_RAW; ++k) memcpy(&staging[(size_t)k * np], cols[k].data(), sizeof(double) * n);
+    if (!hip_ok(hipMemcpyAsync(d_raw.p, staging.data(), sizeof(double) * staging.size(), hipMemcpyHostToDevice, c->s_main), "H2D raw") ||
+        !hip_ok(hipMemsetAsync(c->d_el.p, 0, sizeof(double) * AZ_NUM_FIELDS * np, c->s_main), "memset el") ||
+        !hip_ok(hipMemsetAsync(c->d_flags.p, 0, sizeof(unsigned) * np, c->s_main), "memset flags"))
+        return AZ_ERR_HIP;
+    hipLaunchKernelGGL(k_init, dim3((unsigned)(np / 64)), dim3(64), 0, c->s_main, d_raw.p, n, np, c->g, c->d_el.p, c->d_flags.p);
+    if (!hip_ok(hipGetLastError(), "k_init launch")) return AZ_ERR_HIP;
+    c->h_flags.resize(n);
+    if (np <= kHostMirrorPad) { // (host route of few-point calls: the initialised columns travel back with the status words)
+        c->h_el.resize((size_t)AZ_NUM_FIELDS * np);
+        if (!hip_ok(hipMemcpyAsync(c->h_el.data(), c->d_el.p, sizeof(double) * c->h_el.size(), hipMemcpyDeviceToHost, c->s_main), "D2H el"))
+            return AZ_ERR_HIP;
+    }
+    if (!hip_ok(hipMemcpyAsync(c->h_flags.data(), c->d_flags.p, sizeof(unsigned) * n, hipMemcpyDeviceToHost, c->s_main), "D2H flags") ||
+        !hip_ok(hipStreamSynchronize(c->s_main), "sync(init)"))
+        return AZ_ERR_HIP;
+    c->h_epoch = cols[R_epoch_jd];
+    for (int k = 0; k < AZ_NUM_RAW; ++k) c->h_raw[k] = cols[k];
+    // launch lists.
+    //  [near-earth]  catalog order, except that inside every group of AZ_BLOCK consecutive
+    //      members (= one workgroup = 4 waves) the members are ordered by eccentricity class.
+    //      A single e = 0.2 satellite needs ~4 Kepler-Newton trips and the wide rotation tier and
+    //      would drag the 63 other lanes of its wave along (4% such members touch 93% of the
+    //      waves of an unsorted catalog); after the in-group ordering they share the group's last
+    //      wave.  The group still writes the same contiguous span of rows.
+    //  [deep-space by resonance class]  uniform integrator branch per wave.
+    //  [failed inits]
+    std::vector<unsigned> list;
+    list.reserve(n);
+    for (size_t s = 0; s < n; ++s)
+        if (AZ_FLAG_ERR(c->h_flags[s]) == 0 && !(c->h_flags[s] & AZ_FLAG_DEEP)) list.push_back((unsigned)s);
+    c->n_sgp4 = (unsigned)list.size();
+    for (size_t g0 = 0; g0 < list.size(); g0 += AZ_BLOCK) {
+        const size_t g1 = std::min(g0 + (size_t)AZ_BLOCK, list.size());
+        std::stable_sort(list.begin() + g0, list.begin() + g1, [&](unsigned x, unsigned y) {
+            return AZ_FLAG_ECLASS(c->h_flags[x]) < AZ_FLAG_ECLASS(c->h_flags[y]);
+        });
+    }
+    {
+        // deep space: order by (resonance class, near-equatorial [Lyddane branch], eccentricity
+        // class) so that the integrator branch, the Lyddane branch and the number of Kepler-Newton
+        // trips are as uniform as possible inside each wave
+        std::vector<unsigned> deep;
+        for (size_t s = 0; s < n; ++s)
+            if (AZ_FLAG_ERR(c->h_flags[s]) == 0 && (c->h_flags[s] & AZ_FLAG_DEEP)) deep.push_back((unsigned)s);
+        const std::vector<double> &incl = cols[R_incl_deg];
+        auto key = [&](unsigned s) {
+            const unsigned f = c->h_flags[s];
+            const unsigned low = incl[s] < 12.5 ? 1u : 0u; // 0.2 rad = 11.46 deg, with margin for the periodics
+            return (AZ_FLAG_IREZ(f) << 4) | (low << 2) | AZ_FLAG_ECLASS(f);
+        };
+        std::stable_sort(deep.begin(), deep.end(), [&](unsigned x, unsigned y) { return key(x) < key(y); });
+        list.insert(list.end(), deep.begin(), deep.end());
+    }
+    c->n_sdp4 = (unsigned)list.size() - c->n_sgp4;
+    for (size_t s = 0; s < n; ++s)
+        if (AZ_FLAG_ERR(c->h_flags[s]) != 0) list.push_back((unsigned)s);
+    c->n_bad = (unsigned)list.size() - c->n_sgp4 - c->n_sdp4;
+    // the near-earth members once more, in catalog order, by eccentricity class: [class 0 | other classes]
+    // (the two instantiations of k_rows_fast)
+    c->off_circ = (unsigned)list.size();
+    for (size_t s = 0; s < n; ++s)
+        if (AZ_FLAG_ERR(c->h_flags[s]) == 0 && !(c->h_flags[s] & AZ_FLAG_DEEP) && AZ_FLAG_ECLASS(c->h_flags[s]) == 0)
+            list.push_back((unsigned)s);
+    c->n_circ = (unsigned)list.size() - c->off_circ;
+    for (size_t s = 0; s < n; ++s)
+        if (AZ_FLAG_ERR(c->h_flags[s]) == 0 && !(c->h_flags[s] & AZ_FLAG_DEEP) && AZ_FLAG_ECLASS(c->h_flags[s]) != 0)
+            list.push_back((unsigned)s);
+    // ... and once in plain catalog order (time-major tiles of 16 consecutive rows, k_tiles_fast)
+    c->off_cat = (unsigned)list.size();
+    for (size_t s = 0; s < n; ++s)
+        if (AZ_FLAG_ERR(c->h_flags[s]) == 0 && !(c->h_flags[s] & AZ_FLAG_DEEP)) list.push_back((unsigned)s);
+    // ... and the deep-space members in plain catalog order: one wave per satellite needs no grouping by branch, and
+    // runs of consecutive rows leave the time-major transposer as single long stores
+    c->off_deep_cat = (unsigned)list.size();
+    for (size_t s = 0; s < n; ++s)
+        if (AZ_FLAG_ERR(c->h_flags[s]) == 0 && (c->h_flags[s] & AZ_FLAG_DEEP)) list.push_back((unsigned)s);
+    // ... and the row map of the time-major tile kernel: what every catalog row is and where its data comes from
+    c->off_rowmap = (unsigned)list.size();
+    {
+        unsigned near = 0, deepn = 0;
+        for (size_t s = 0; s < n; ++s) {
+            const unsigned f = c->h_flags[s];
+            if (AZ_FLAG_ERR(f) != 0) list.push_back((unsigned)AZ_ROW_ZERO << 30);
+            else if (f & AZ_FLAG_DEEP) list.push_back(((unsigned)AZ_ROW_COPY << 30) | deepn++);
+            else list.push_back(((unsigned)AZ_ROW_NEAR << 30) | near++);
+        }
+    }
+    // ... and once more for the lane = satellite time-major kernel, whose plan and redo items count near-earth slots in
+    // the [class 0 | other classes] list: slot < n_circ = computed there, the rest arrive through the scratch array
+    c->off_rowmap2 = (unsigned)list.size();
+    {
+        unsigned circ = 0, eccn = 0, deepn = 0;
+        for (size_t s = 0; s < n; ++s) {
+            const unsigned f = c->h_flags[s];
+            if (AZ_FLAG_ERR(f) != 0) list.push_back((unsigned)AZ_ROW_ZERO << 30);
+            else if (f & AZ_FLAG_DEEP) list.push_back(((unsigned)AZ_ROW_COPY << 30) | deepn++);
+            else if (AZ_FLAG_ECLASS(f) == 0) list.push_back(((unsigned)AZ_ROW_NEAR << 30) | circ++);
+            else list.push_back(((unsigned)AZ_ROW_NEAR << 30) | (c->n_circ + eccn++));
+        }
+    }
+    if (const char *e = getenv("ASTROZ_AMD_COLS")) c->cols_kernel = atoi(e);
+    if (const char *e = getenv("ASTROZ_AMD_GRAPHS")) c->graphs_on = atoi(e);
+    c->h_list = list;
+    if (c->d_list.ensure(list.size()) != AZ_OK ||
+        !hip_ok(hipMemcpy(c->d_list.p, list.data(), sizeof(unsigned) * list.size(), hipMemcpyHostToDevice), "H2D list"))
+        return AZ_ERR_HIP;
+    *out = c.release();
     return AZ_OK;
 }
 
@@ -991,11 +973,11 @@ int32_t stage_inputs(azh_constellation *c, const double *times, size_t n_times, 
         }
         if (uni) {
             if (c->d_inc.ensure((size_t)2 * AZ_INC_NUM * c->n_pad) != AZ_OK) return AZ_ERR_HIP;
-            hipLaunchKernelGGL(k_prep_inc, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, st, c->d_el, c->n, c->n_pad,
+            hipLaunchKernelGGL(k_prep_inc, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, st, c->d_el.p, c->n, c->n_pad,
                                step, c->d_inc.p);
             HIP_TRY(hipGetLastError());
             if (c->d_fast_rec.ensure((size_t)FR_NUM * c->n_pad) != AZ_OK) return AZ_ERR_HIP;
-            hipLaunchKernelGGL(k_prep_rec, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, st, c->d_el, c->d_flags, c->n, c->n_pad,
+            hipLaunchKernelGGL(k_prep_rec, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, st, c->d_el.p, c->d_flags.p, c->n, c->n_pad,
                                c->d_inc.p, c->d_fast_rec.p);
             HIP_TRY(hipGetLastError());
             c->uniform_step = step;
@@ -1038,7 +1020,7 @@ int32_t prepare_deep(azh_constellation *c, PropArgs &d, hipStream_t st, bool row
             if (c->d_node_cache.ensure(3 * c->n_pad) != AZ_OK) return AZ_ERR_HIP;
             HIP_TRY(hipMemsetAsync(c->d_node_cache.p, 0, sizeof(double) * 3 * c->n_pad, st)); // atime = 0: start from epoch
         }
-        hipLaunchKernelGGL(k_deep_seed, dim3((c->n_sdp4 + 63) / 64), dim3(64), 0, st, c->d_el, c->d_flags, c->n_pad,
+        hipLaunchKernelGGL(k_deep_seed, dim3((c->n_sdp4 + 63) / 64), dim3(64), 0, st, c->d_el.p, c->d_flags.p, c->n_pad,
                            d.list, c->n_sdp4, d.times, n_times, d.offsets, seed_tile, c->d_seeds.p, rows ? 1 : 0, c->d_node_cache.p);
         HIP_TRY(hipGetLastError());
         c->seeds_valid = true;
@@ -1093,14 +1075,28 @@ int32_t ensure_plan(azh_constellation *c, PropArgs &a, const FastShape &shape, h
     return AZ_OK;
 }
 
+// the only way captured launch sets go: once no replay of them can still be running (ev_graph: never a wait on the stream of
+// a replay, which is the caller's and may be gone).  Nothing to wait for -- or to do -- while the cache is empty: small
+// handles are never captured, and graphs are off by default.
 void drop_graphs(azh_constellation *c)
 {
+    if (c->graphs.empty()) return;
+    if (hipEventSynchronize(c->ev_graph) != hipSuccess) (void)hipGetLastError();
     for (auto &g : c->graphs) {
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
         if (g.graph) (void)hipGraphDestroy(g.graph);
     }
     c->graphs.clear();
 }
+} // namespace
+
+azh_constellation::~azh_constellation()
+{
+    (void)hipSetDevice(device);
+    drop_graphs(this);
+}
+
+namespace {
 unsigned plan_sig(const azh_constellation *c)
 {
     unsigned s = 0;
@@ -1120,8 +1116,8 @@ int32_t launch_all(azh_constellation *c, double *d_pos, double *d_vel, int layou
     if (layout == AZ_LAYOUT_TIME_MAJOR && stride < c->n) return AZ_ERR_VALUE;
 
     PropArgs a{};
-    a.el = c->d_el;
-    a.flags = c->d_flags;
+    a.el = c->d_el.p;
+    a.flags = c->d_flags.p;
     a.n_pad = c->n_pad;
     a.times = c->d_times.p;
     a.n_times = n_times;
@@ -1180,8 +1176,8 @@ int32_t launch_all(azh_constellation *c, double *d_pos, double *d_vel, int layou
     auto ensure_scratch = [&](hipStream_t user) -> int32_t {
         if (c->capturing && c->d_deep_tmp.cap < scratch_words * (d_vel ? 2 : 1)) return AZ_RC_EAGER;
         if (c->d_deep_tmp.cap < scratch_words * (d_vel ? 2 : 1)) {
-            HIP_TRY(hipStreamSynchronize(user));
             drop_graphs(c); // (captured launch sets hold the old scratch pointer: ADVICE r05)
+            HIP_TRY(hipStreamSynchronize(user)); // (launches in flight use the old buffer)
         }
         if (c->d_deep_tmp.ensure(scratch_words * (d_vel ? 2 : 1)) != AZ_OK) return AZ_ERR_HIP;
         a.tmp_pos = c->d_deep_tmp.p;
@@ -1264,7 +1260,7 @@ int32_t launch_all(azh_constellation *c, double *d_pos, double *d_vel, int layou
     }
     if (c->n_bad > 0) {
         hipLaunchKernelGGL(k_fill_bad, dim3((n_times + 255) / 256, c->n_bad), dim3(256), 0, st,
-                           c->d_list.p + c->n_sgp4 + c->n_sdp4, c->n_bad, c->d_flags, n_times, d_pos, d_vel, d_err,
+                           c->d_list.p + c->n_sgp4 + c->n_sdp4, c->n_bad, c->d_flags.p, n_times, d_pos, d_vel, d_err,
                            c->have_mask ? c->d_mask.p : nullptr, layout, stride, f32, a.row_lo, a.row_hi);
         HIP_TRY(hipGetLastError());
     }
@@ -1284,7 +1280,7 @@ int32_t launch_cached(azh_constellation *c, double *d_pos, double *d_vel, int la
                       int f32 = 0, size_t row_lo = 0, size_t row_hi = ~(size_t)0)
 {
     // (a small handle launches on its device's shared stream: no capture there)
-    if (!c->graphs_on || c->timing || c->cached_n_times == 0 || !c->own_stream) return launch_all(c, d_pos, d_vel, layout, stride, d_err, st, f32, row_lo, row_hi);
+    if (!c->graphs_on || c->timing || c->cached_n_times == 0 || !c->s_main.owned()) return launch_all(c, d_pos, d_vel, layout, stride, d_err, st, f32, row_lo, row_hi);
     const unsigned sig = plan_sig(c);
     azh_constellation::LaunchGraph *hit = nullptr, *pending = nullptr;
     for (auto &g : c->graphs)
@@ -1298,6 +1294,7 @@ int32_t launch_cached(azh_constellation *c, double *d_pos, double *d_vel, int la
         HIP_TRY(hipGraphLaunch(hit->exec, st));
         for (unsigned k = 0; k < 4; ++k) c->plan[k].parity = (hit->sig_after >> k) & 1u;
         c->last_path = hit->path;
+        HIP_TRY(hipEventRecord(c->ev_graph, st));
         return AZ_OK;
     }
     if (!pending) {
@@ -1340,6 +1337,7 @@ int32_t launch_cached(azh_constellation *c, double *d_pos, double *d_vel, int la
     pending->sig_after = plan_sig(c);
     pending->path = c->last_path;
     HIP_TRY(hipGraphLaunch(exec, st));
+    HIP_TRY(hipEventRecord(c->ev_graph, st));
     return AZ_OK;
 }
 
@@ -1547,13 +1545,13 @@ int32_t copy_back_staged(HostStager &hs, void *const *dst, const void *const *sr
     std::vector<size_t> ticket(chunks.size(), 0);
     auto land = [&](size_t i) -> int32_t { // chunk i has been issued into slot i % S: wait for it, move it out
         HIP_TRY(hipEventSynchronize(hs.ev[i % kStageSlots]));
-        if (pooled) ticket[i] = pool.submit(chunks[i].dst, static_cast<const char *>(hs.slot[i % kStageSlots]), chunks[i].len);
-        else memcpy(chunks[i].dst, hs.slot[i % kStageSlots], chunks[i].len);
+        if (pooled) ticket[i] = pool.submit(chunks[i].dst, static_cast<const char *>(hs.slot[i % kStageSlots].p), chunks[i].len);
+        else memcpy(chunks[i].dst, hs.slot[i % kStageSlots].p, chunks[i].len);
         return AZ_OK;
     };
     for (size_t i = 0; i < chunks.size(); ++i) {
         if (pooled && i >= (size_t)kStageSlots) pool.wait(ticket[i - kStageSlots]); // the slot is free again
-        HIP_TRY(hipMemcpyAsync(hs.slot[i % kStageSlots], chunks[i].src, chunks[i].len, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(hs.slot[i % kStageSlots].p, chunks[i].src, chunks[i].len, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipEventRecord(hs.ev[i % kStageSlots], st));
         // (inline mode: chunk i - 1 is moved out while chunk i is on the link; with S >= 2 slots its slot is not reused before)
         if (i >= 1)
@@ -1596,17 +1594,17 @@ int32_t launch_one(azh_constellation *c, size_t sat, const double *d_t, size_t n
         c->one_segments = n_seg;
         HIP_TRY(hipMemsetAsync(c->d_one_items.p, 0, sizeof(unsigned) * AZ_ONE_HEAD, st));
         if (d_v)
-            hipLaunchKernelGGL((k_one_fast<true>), dim3(n_seg), dim3(64), 0, st, c->d_el, c->d_flags, c->n_pad, (unsigned)sat, d_t,
+            hipLaunchKernelGGL((k_one_fast<true>), dim3(n_seg), dim3(64), 0, st, c->d_el.p, c->d_flags.p, c->n_pad, (unsigned)sat, d_t,
                                (unsigned)n, d_p, d_v, d_e, c->g, (const double *)nullptr, c->d_one_items.p, cap);
         else
-            hipLaunchKernelGGL((k_one_fast<false>), dim3(n_seg), dim3(64), 0, st, c->d_el, c->d_flags, c->n_pad, (unsigned)sat, d_t,
+            hipLaunchKernelGGL((k_one_fast<false>), dim3(n_seg), dim3(64), 0, st, c->d_el.p, c->d_flags.p, c->n_pad, (unsigned)sat, d_t,
                                (unsigned)n, d_p, d_v, d_e, c->g, (const double *)nullptr, c->d_one_items.p, cap);
         HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL((k_one_satellite<true>), dim3(4096), dim3(64), 0, st, c->d_el, c->d_flags, c->n_pad, (unsigned)sat, d_t,
+        hipLaunchKernelGGL((k_one_satellite<true>), dim3(4096), dim3(64), 0, st, c->d_el.p, c->d_flags.p, c->n_pad, (unsigned)sat, d_t,
                            (unsigned)n, d_p, d_v, d_e, 0, c->g, (const double *)nullptr, 0, (const unsigned *)c->d_one_items.p, cap);
         HIP_TRY(hipEventRecord(c->ev_one, st));
     } else {
-        hipLaunchKernelGGL((k_one_satellite<false>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, c->d_el, c->d_flags, c->n_pad,
+        hipLaunchKernelGGL((k_one_satellite<false>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, c->d_el.p, c->d_flags.p, c->n_pad,
                            (unsigned)sat, d_t, (unsigned)n, d_p, d_v, d_e, interleaved, c->g, (const double *)nullptr, 0,
                            (const unsigned *)nullptr);
     }
@@ -1624,6 +1622,7 @@ int32_t launch_one(azh_constellation *c, size_t sat, const double *d_t, size_t n
 #define AZ_ONE_ZERO_COPY_MAX 16384
 #endif
 constexpr size_t kOneStage = 16384;
+constexpr size_t kOnePointBytes = 7 * sizeof(double) + 8; // per staged point: the time, six outputs, the status byte (padded)
 constexpr size_t kSmallOut = size_t(512) << 10; // bytes of results a host-returning constellation call lets its kernels write to pinned host memory directly
 constexpr size_t kOneZeroCopy = AZ_ONE_ZERO_COPY_MAX; // points the kernel exchanges with the pinned buffer directly
 
@@ -1652,7 +1651,7 @@ const double *host_column(azh_constellation *c, size_t sat, size_t &n_pad, size_
             c->h_el.clear();
         }
         if (!c->h_el.empty()) {
-            if (hip_ok(hipMemcpy(c->h_el.data(), c->d_el, sizeof(double) * c->h_el.size(), hipMemcpyDeviceToHost), "D2H table")) {
+            if (hip_ok(hipMemcpy(c->h_el.data(), c->d_el.p, sizeof(double) * c->h_el.size(), hipMemcpyDeviceToHost), "D2H table")) {
                 c->h_cols.clear();
                 n_pad = c->n_pad;
                 col = sat;
@@ -1664,7 +1663,7 @@ const double *host_column(azh_constellation *c, size_t sat, size_t &n_pad, size_
     n_pad = 1;
     col = 0;
     std::vector<double> f(AZ_NUM_FIELDS);
-    if (!hip_ok(hipMemcpy2D(f.data(), sizeof(double), c->d_el + sat, sizeof(double) * c->n_pad, sizeof(double), AZ_NUM_FIELDS,
+    if (!hip_ok(hipMemcpy2D(f.data(), sizeof(double), c->d_el.p + sat, sizeof(double) * c->n_pad, sizeof(double), AZ_NUM_FIELDS,
                             hipMemcpyDeviceToHost), "D2H column"))
         return nullptr;
     if (c->h_cols.size() < kHostCols) {
@@ -1701,17 +1700,9 @@ int32_t run_one_satellite(azh_constellation *c, size_t sat, const double *tsince
     hipStream_t st = c->s_main;
     if (c->d_one_t.ensure(n) != AZ_OK || c->d_one_o.ensure(6 * n) != AZ_OK || c->d_one_e.ensure(n) != AZ_OK) return AZ_ERR_HIP;
     const bool staged = n <= kOneStage;
-    if (staged && c->h_stage_cap < n) {
-        size_t cap = std::max<size_t>(c->h_stage_cap, 1024);
-        while (cap < n) cap *= 2;
-        if (c->h_stage) (void)hipHostFree(c->h_stage);
-        c->h_stage = nullptr;
-        c->h_stage_cap = 0;
-        HIP_TRY(hipHostMalloc(&c->h_stage, cap * (7 * sizeof(double) + 8), hipHostMallocDefault));
-        c->h_stage_cap = cap;
-    }
-    const size_t scap = c->h_stage_cap;
-    double *hs_t = static_cast<double *>(c->h_stage);
+    if (staged && c->h_stage.ensure(n * kOnePointBytes) != AZ_OK) return AZ_ERR_HIP;
+    const size_t scap = c->h_stage.cap / kOnePointBytes;
+    double *hs_t = static_cast<double *>(c->h_stage.p);
     double *hs_o = hs_t ? hs_t + scap : nullptr;
     uint8_t *hs_e = hs_o ? reinterpret_cast<uint8_t *>(hs_o + 6 * scap) : nullptr;
     double *d_p = c->d_one_o.p, *d_v = c->d_one_o.p + 3 * n;
@@ -1947,7 +1938,7 @@ int32_t azh_constellation_subset(const azh_constellation *c, const uint32_t *ind
     });
 }
 
-void azh_constellation_free(azh_constellation *c) { destroy(c); }
+void azh_constellation_free(azh_constellation *c) { delete c; }
 
 size_t azh_num_satellites(const azh_constellation *c) { return c ? c->n : 0; }
 size_t azh_num_sgp4(const azh_constellation *c) { return c ? c->n_sgp4 : 0; }
@@ -1978,7 +1969,7 @@ int32_t azh_get_field(const azh_constellation *c, const char *name, double *out)
     for (int k = 0; k < AZ_NUM_FIELDS; ++k) {
         if (strcmp(kFieldNames[k], name) == 0) {
             if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
-            HIP_TRY(hipMemcpy(out, c->d_el + (size_t)k * c->n_pad, sizeof(double) * c->n, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(out, c->d_el.p + (size_t)k * c->n_pad, sizeof(double) * c->n, hipMemcpyDeviceToHost));
             return AZ_OK;
         }
     }
@@ -2056,90 +2047,63 @@ int32_t azh_set_graphs(azh_constellation *c, int32_t enabled)
     return AZ_OK;
 }
 
-static int32_t azh_propagate_device_impl(azh_constellation *c, const double *times, size_t n_times, const double *offsets,
-                             double *d_pos, double *d_vel, int32_t mode, double reference_jd, const uint8_t *mask,
-                             int32_t layout, size_t stride, uint8_t *d_err, void *stream)
+// azh_propagate_device / _f32 (f32: the outputs are floats)
+static int32_t propagate_device(azh_constellation *c, const double *times, size_t n_times, const double *offsets, double *d_pos,
+                                double *d_vel, int32_t mode, double reference_jd, const uint8_t *mask, int32_t layout, size_t stride,
+                                uint8_t *d_err, void *stream, int f32)
 {
-    if (!c || !d_pos || (n_times && !times)) return AZ_ERR_NULL_POINTER;
-    if (mode < 0 || mode > 2 || layout < 0 || layout > 1) return AZ_ERR_VALUE;
-    if (n_times == 0) return AZ_OK; // an empty grid is valid and produces nothing
-    if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
-    hipStream_t st = stream ? (hipStream_t)stream : c->s_main;
-    int32_t rc = stage_inputs(c, times, n_times, offsets, mask, mode, reference_jd, st);
-    if (rc != AZ_OK) return rc;
-    return launch_all(c, d_pos, d_vel, layout, stride, d_err, st);
+    return guarded([&]() -> int32_t {
+        if (!c || !d_pos || (n_times && !times)) return AZ_ERR_NULL_POINTER;
+        if (mode < 0 || mode > 2 || layout < 0 || layout > 1) return AZ_ERR_VALUE;
+        if (n_times == 0) return AZ_OK; // an empty grid is valid and produces nothing
+        if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
+        hipStream_t st = stream ? (hipStream_t)stream : c->s_main;
+        int32_t rc = stage_inputs(c, times, n_times, offsets, mask, mode, reference_jd, st);
+        if (rc != AZ_OK) return rc;
+        return launch_all(c, d_pos, d_vel, layout, stride, d_err, st, f32);
+    });
 }
 int32_t azh_propagate_device(azh_constellation *c, const double *times, size_t n_times, const double *offsets,
                              double *d_pos, double *d_vel, int32_t mode, double reference_jd, const uint8_t *mask,
                              int32_t layout, size_t stride, uint8_t *d_err, void *stream)
 {
-    return guarded([&]() -> int32_t { return azh_propagate_device_impl(c, times, n_times, offsets, d_pos, d_vel, mode, reference_jd, mask, layout, stride, d_err, stream); });
-}
-
-static int32_t azh_propagate_device_cached_impl(azh_constellation *c, double *d_pos, double *d_vel, int32_t layout,
-                                    size_t stride, uint8_t *d_err, void *stream)
-{
-    if (!c || !d_pos) return AZ_ERR_NULL_POINTER;
-    if (layout < 0 || layout > 1) return AZ_ERR_VALUE;
-    if (c->cached_n_times == 0) return AZ_ERR_NOT_INITIALIZED;
-    if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
-    return launch_cached(c, d_pos, d_vel, layout, stride, d_err, stream ? (hipStream_t)stream : c->s_main);
-}
-int32_t azh_propagate_device_cached(azh_constellation *c, double *d_pos, double *d_vel, int32_t layout,
-                                    size_t stride, uint8_t *d_err, void *stream)
-{
-    return guarded([&]() -> int32_t { return azh_propagate_device_cached_impl(c, d_pos, d_vel, layout, stride, d_err, stream); });
-}
-
-static int32_t azh_propagate_device_window_impl(azh_constellation *c, size_t row_lo, size_t row_hi, double *d_pos, double *d_vel,
-                                    int32_t layout, size_t stride, uint8_t *d_err, void *stream)
-{
-    if (!c || !d_pos) return AZ_ERR_NULL_POINTER;
-    if (layout < 0 || layout > 1) return AZ_ERR_VALUE;
-    if (c->cached_n_times == 0) return AZ_ERR_NOT_INITIALIZED;
-    if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
-    return launch_cached(c, d_pos, d_vel, layout, stride, d_err, stream ? (hipStream_t)stream : c->s_main, 0, row_lo, row_hi);
-}
-int32_t azh_propagate_device_window(azh_constellation *c, size_t row_lo, size_t row_hi, double *d_pos, double *d_vel,
-                                    int32_t layout, size_t stride, uint8_t *d_err, void *stream)
-{
-    return guarded([&]() -> int32_t { return azh_propagate_device_window_impl(c, row_lo, row_hi, d_pos, d_vel, layout, stride, d_err, stream); });
-}
-
-static int32_t azh_propagate_device_f32_impl(azh_constellation *c, const double *times, size_t n_times, const double *offsets,
-                                 float *d_pos, float *d_vel, int32_t mode, double reference_jd, const uint8_t *mask,
-                                 int32_t layout, size_t stride, uint8_t *d_err, void *stream)
-{
-    if (!c || !d_pos || (n_times && !times)) return AZ_ERR_NULL_POINTER;
-    if (mode < 0 || mode > 2 || layout < 0 || layout > 1) return AZ_ERR_VALUE;
-    if (n_times == 0) return AZ_OK;
-    if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
-    hipStream_t st = stream ? (hipStream_t)stream : c->s_main;
-    int32_t rc = stage_inputs(c, times, n_times, offsets, mask, mode, reference_jd, st);
-    if (rc != AZ_OK) return rc;
-    return launch_all(c, reinterpret_cast<double *>(d_pos), reinterpret_cast<double *>(d_vel), layout, stride, d_err, st, 1);
+    return propagate_device(c, times, n_times, offsets, d_pos, d_vel, mode, reference_jd, mask, layout, stride, d_err, stream, 0);
 }
 int32_t azh_propagate_device_f32(azh_constellation *c, const double *times, size_t n_times, const double *offsets,
                                  float *d_pos, float *d_vel, int32_t mode, double reference_jd, const uint8_t *mask,
                                  int32_t layout, size_t stride, uint8_t *d_err, void *stream)
 {
-    return guarded([&]() -> int32_t { return azh_propagate_device_f32_impl(c, times, n_times, offsets, d_pos, d_vel, mode, reference_jd, mask, layout, stride, d_err, stream); });
+    return propagate_device(c, times, n_times, offsets, reinterpret_cast<double *>(d_pos), reinterpret_cast<double *>(d_vel), mode,
+                            reference_jd, mask, layout, stride, d_err, stream, 1);
 }
 
-static int32_t azh_propagate_device_cached_f32_impl(azh_constellation *c, float *d_pos, float *d_vel, int32_t layout, size_t stride,
-                                        uint8_t *d_err, void *stream)
+// azh_propagate_device_cached / _window / _cached_f32: the staged inputs again, rows [row_lo, row_hi)
+static int32_t propagate_cached(azh_constellation *c, size_t row_lo, size_t row_hi, double *d_pos, double *d_vel, int32_t layout,
+                                size_t stride, uint8_t *d_err, void *stream, int f32)
 {
-    if (!c || !d_pos) return AZ_ERR_NULL_POINTER;
-    if (layout < 0 || layout > 1) return AZ_ERR_VALUE;
-    if (c->cached_n_times == 0) return AZ_ERR_NOT_INITIALIZED;
-    if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
-    return launch_cached(c, reinterpret_cast<double *>(d_pos), reinterpret_cast<double *>(d_vel), layout, stride, d_err,
-                         stream ? (hipStream_t)stream : c->s_main, 1);
+    return guarded([&]() -> int32_t {
+        if (!c || !d_pos) return AZ_ERR_NULL_POINTER;
+        if (layout < 0 || layout > 1) return AZ_ERR_VALUE;
+        if (c->cached_n_times == 0) return AZ_ERR_NOT_INITIALIZED;
+        if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
+        return launch_cached(c, d_pos, d_vel, layout, stride, d_err, stream ? (hipStream_t)stream : c->s_main, f32, row_lo, row_hi);
+    });
+}
+int32_t azh_propagate_device_cached(azh_constellation *c, double *d_pos, double *d_vel, int32_t layout,
+                                    size_t stride, uint8_t *d_err, void *stream)
+{
+    return propagate_cached(c, 0, ~(size_t)0, d_pos, d_vel, layout, stride, d_err, stream, 0);
+}
+int32_t azh_propagate_device_window(azh_constellation *c, size_t row_lo, size_t row_hi, double *d_pos, double *d_vel,
+                                    int32_t layout, size_t stride, uint8_t *d_err, void *stream)
+{
+    return propagate_cached(c, row_lo, row_hi, d_pos, d_vel, layout, stride, d_err, stream, 0);
 }
 int32_t azh_propagate_device_cached_f32(azh_constellation *c, float *d_pos, float *d_vel, int32_t layout, size_t stride,
                                         uint8_t *d_err, void *stream)
 {
-    return guarded([&]() -> int32_t { return azh_propagate_device_cached_f32_impl(c, d_pos, d_vel, layout, stride, d_err, stream); });
+    return propagate_cached(c, 0, ~(size_t)0, reinterpret_cast<double *>(d_pos), reinterpret_cast<double *>(d_vel), layout, stride,
+                            d_err, stream, 1);
 }
 
 // Fused single-target conjunction screen (Constellation.screenConstellation, src/Constellation.zig
@@ -2162,7 +2126,7 @@ static int32_t screen_core(azh_constellation *c, const double *times, size_t n_t
     if (c->timing) HIP_TRY(hipEventRecord(c->ev_t0, st));
     const unsigned nb_fill = ((unsigned)c->n + 255) / 256;
     if (nt == 0) {
-        hipLaunchKernelGGL(k_screen_prep, dim3(nb_fill), dim3(64), 0, st, c->d_el, c->d_flags, c->n_pad, 0u, (const double *)nullptr, 0u,
+        hipLaunchKernelGGL(k_screen_prep, dim3(nb_fill), dim3(64), 0, st, c->d_el.p, c->d_flags.p, c->n_pad, 0u, (const double *)nullptr, 0u,
                            (const double *)nullptr, c->g, (double *)nullptr, 0u, (size_t)0, (double *)nullptr, (unsigned *)nullptr, 0u,
                            (unsigned)c->n, threshold_km, d_min_dist, d_min_t);
         HIP_TRY(hipGetLastError());
@@ -2170,8 +2134,8 @@ static int32_t screen_core(azh_constellation *c, const double *times, size_t n_t
     if (nt > 0) {
         if (!d_track && c->d_tgt.ensure((size_t)nt * 3) != AZ_OK) return AZ_ERR_HIP;
         PropArgs a{};
-        a.el = c->d_el;
-        a.flags = c->d_flags;
+        a.el = c->d_el.p;
+        a.flags = c->d_flags.p;
         a.n_pad = c->n_pad;
         a.times = c->d_times.p;
         a.n_times = nt;
@@ -2232,7 +2196,7 @@ static int32_t screen_core(azh_constellation *c, const double *times, size_t n_t
             const unsigned nb_track = d_track ? 0u : (nt + 63) / 64;
             const size_t n_clear = fast_screen ? np_near : 0;
             const unsigned nb_clear = (unsigned)((n_clear + 255) / 256);
-            hipLaunchKernelGGL(k_screen_prep, dim3(nb_track + nb_clear + nb_fill), dim3(64), 0, st, c->d_el, c->d_flags, c->n_pad,
+            hipLaunchKernelGGL(k_screen_prep, dim3(nb_track + nb_clear + nb_fill), dim3(64), 0, st, c->d_el.p, c->d_flags.p, c->n_pad,
                                (unsigned)(d_track ? 0 : target), c->d_times.p, nt, c->have_offsets ? c->d_offsets.p : (const double *)nullptr, c->g,
                                c->d_tgt.p, nb_track, n_clear, near.part_d2, near.part_t, nb_clear, (unsigned)c->n, threshold_km, d_min_dist, d_min_t);
             HIP_TRY(hipGetLastError());
@@ -2302,53 +2266,41 @@ int32_t azh_screen_track_device(azh_constellation *c, const double *times, size_
     });
 }
 
-static int32_t azh_screen_target_host_impl(azh_constellation *c, const double *times, size_t n_times, const double *offsets,
-                               size_t target, double threshold_km, double reference_jd, double *min_dist,
-                               uint32_t *min_t)
-{
-    if (!c || !min_dist || !min_t) return AZ_ERR_NULL_POINTER;
-    if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
-    // results of up to kSmallOut bytes (43,000 satellites): the finalisation kernel writes them into a pinned host buffer of the
-    // handle ITSELF (device-addressable, coherent) and one synchronize ends the call -- two pageable device-to-host copies of
-    // a hundred KB cost 15-20 us each behind a 0.18-ms screen
-    const size_t small_total = c->n * (sizeof(double) + sizeof(uint32_t)) + 64;
-    if (small_total <= kSmallOut) {
-        if (c->h_small_cap < small_total) {
-            HIP_TRY(hipStreamSynchronize(c->s_main));
-            if (c->h_small) (void)hipHostFree(c->h_small);
-            c->h_small = nullptr;
-            c->h_small_cap = 0;
-            size_t cap = 65536;
-            while (cap < small_total) cap *= 2;
-            HIP_TRY(hipHostMalloc(&c->h_small, cap, hipHostMallocDefault));
-            c->h_small_cap = cap;
-        }
-        double *hd = static_cast<double *>(c->h_small);
-        uint32_t *ht = reinterpret_cast<uint32_t *>(hd + ((c->n + 7) & ~size_t(7)));
-        double *dd = nullptr;
-        HIP_TRY(hipHostGetDevicePointer((void **)&dd, hd, 0));
-        uint32_t *dt = reinterpret_cast<uint32_t *>(dd + (reinterpret_cast<double *>(ht) - hd));
-        int32_t rc = azh_screen_target_device(c, times, n_times, offsets, target, threshold_km, reference_jd, dd, dt, nullptr);
-        if (rc != AZ_OK) return rc;
-        HIP_TRY(hipStreamSynchronize(c->s_main));
-        memcpy(min_dist, hd, sizeof(double) * c->n);
-        memcpy(min_t, ht, sizeof(uint32_t) * c->n);
-        return AZ_OK;
-    }
-    if (c->d_out_d.ensure(c->n) != AZ_OK || c->d_out_t.ensure(c->n) != AZ_OK) return AZ_ERR_HIP;
-    int32_t rc = azh_screen_target_device(c, times, n_times, offsets, target, threshold_km, reference_jd, c->d_out_d.p,
-                                          c->d_out_t.p, nullptr);
-    if (rc != AZ_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(min_dist, c->d_out_d.p, sizeof(double) * c->n, hipMemcpyDeviceToHost, c->s_main));
-    HIP_TRY(hipMemcpyAsync(min_t, c->d_out_t.p, sizeof(uint32_t) * c->n, hipMemcpyDeviceToHost, c->s_main));
-    HIP_TRY(hipStreamSynchronize(c->s_main));
-    return AZ_OK;
-}
 int32_t azh_screen_target_host(azh_constellation *c, const double *times, size_t n_times, const double *offsets,
                                size_t target, double threshold_km, double reference_jd, double *min_dist,
                                uint32_t *min_t)
 {
-    return guarded([&]() -> int32_t { return azh_screen_target_host_impl(c, times, n_times, offsets, target, threshold_km, reference_jd, min_dist, min_t); });
+    return guarded([&]() -> int32_t {
+        if (!c || !min_dist || !min_t) return AZ_ERR_NULL_POINTER;
+        if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
+        // results of up to kSmallOut bytes (43,000 satellites): the finalisation kernel writes them into a pinned host buffer of the
+        // handle ITSELF (device-addressable, coherent) and one synchronize ends the call -- two pageable device-to-host copies of
+        // a hundred KB cost 15-20 us each behind a 0.18-ms screen
+        const size_t small_total = c->n * (sizeof(double) + sizeof(uint32_t)) + 64;
+        if (small_total <= kSmallOut) {
+            if (c->h_small.cap < small_total) HIP_TRY(hipStreamSynchronize(c->s_main));
+            if (c->h_small.ensure(small_total) != AZ_OK) return AZ_ERR_HIP;
+            double *hd = static_cast<double *>(c->h_small.p);
+            uint32_t *ht = reinterpret_cast<uint32_t *>(hd + ((c->n + 7) & ~size_t(7)));
+            double *dd = nullptr;
+            HIP_TRY(hipHostGetDevicePointer((void **)&dd, hd, 0));
+            uint32_t *dt = reinterpret_cast<uint32_t *>(dd + (reinterpret_cast<double *>(ht) - hd));
+            int32_t rc = azh_screen_target_device(c, times, n_times, offsets, target, threshold_km, reference_jd, dd, dt, nullptr);
+            if (rc != AZ_OK) return rc;
+            HIP_TRY(hipStreamSynchronize(c->s_main));
+            memcpy(min_dist, hd, sizeof(double) * c->n);
+            memcpy(min_t, ht, sizeof(uint32_t) * c->n);
+            return AZ_OK;
+        }
+        if (c->d_out_d.ensure(c->n) != AZ_OK || c->d_out_t.ensure(c->n) != AZ_OK) return AZ_ERR_HIP;
+        int32_t rc = azh_screen_target_device(c, times, n_times, offsets, target, threshold_km, reference_jd, c->d_out_d.p,
+                                              c->d_out_t.p, nullptr);
+        if (rc != AZ_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(min_dist, c->d_out_d.p, sizeof(double) * c->n, hipMemcpyDeviceToHost, c->s_main));
+        HIP_TRY(hipMemcpyAsync(min_t, c->d_out_t.p, sizeof(uint32_t) * c->n, hipMemcpyDeviceToHost, c->s_main));
+        HIP_TRY(hipStreamSynchronize(c->s_main));
+        return AZ_OK;
+    });
 }
 
 // All-vs-all coarse screen of device-resident positions (coarseScreen, bindings/python/src/
@@ -2386,11 +2338,11 @@ int32_t coarse_screen(const double *d_pos, size_t n_sats, size_t n_times, int32_
         DevBuf<uint8_t> valid;
     };
     static std::mutex table_mu;
-    static std::map<int, std::unique_ptr<Scratch>> per_device;
+    static auto *per_device = new std::map<int, std::unique_ptr<Scratch>>(); // (never destroyed: see the owner types)
     Scratch *S = nullptr;
     {
         std::lock_guard<std::mutex> lk(table_mu);
-        auto &slot = per_device[dev_id];
+        auto &slot = (*per_device)[dev_id];
         if (!slot) slot.reset(new Scratch());
         S = slot.get();
     }
@@ -2494,196 +2446,173 @@ int32_t azh_coarse_screen_host(const double *pos, size_t n_sats, size_t n_times,
     if (stride == 0) stride = n_sats;
     const size_t rows = (layout == AZ_LAYOUT_TIME_MAJOR) ? stride : n_sats;
     const size_t bytes = rows * n_times * 3 * sizeof(double);
-    double *d_pos = nullptr;
     if (bytes == 0) { *n_found = 0; return AZ_OK; }
-    HIP_TRY(hipMalloc((void **)&d_pos, bytes));
-    int32_t rc = AZ_OK;
-    if (!hip_ok(hipMemcpy(d_pos, pos, bytes, hipMemcpyHostToDevice), "H2D pos")) rc = AZ_ERR_HIP;
-    if (rc == AZ_OK)
-        rc = azh_coarse_screen_device(d_pos, n_sats, n_times, layout, stride, threshold_km, valid_mask, out_pairs, out_t,
-                                      max_results, n_found, nullptr);
-    (void)hipFree(d_pos);
-    return rc;
+    DevBuf<double> d_pos;
+    if (d_pos.ensure(bytes / sizeof(double)) != AZ_OK) return AZ_ERR_HIP;
+    if (!hip_ok(hipMemcpy(d_pos.p, pos, bytes, hipMemcpyHostToDevice), "H2D pos")) return AZ_ERR_HIP;
+    return azh_coarse_screen_device(d_pos.p, n_sats, n_times, layout, stride, threshold_km, valid_mask, out_pairs, out_t,
+                                    max_results, n_found, nullptr);
 }
 
 // screen() without a target (bindings/python/astroz/__init__.py L633-658): propagate every member
 // to TEME on the device (time-major scratch, never copied to the host) and run the coarse screen on it
-static int32_t azh_screen_all_host_impl(azh_constellation *c, const double *times, size_t n_times, const double *offsets,
-                            double threshold_km, uint32_t *out_pairs, uint32_t *out_t, size_t max_results,
-                            size_t *n_found)
-{
-    if (!c || !n_found || (n_times && !times)) return AZ_ERR_NULL_POINTER;
-    *n_found = 0;
-    if (n_times == 0) return AZ_OK;
-    if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
-    // (the handle's grow-only result buffer: no 39-MB hipMalloc / hipFree pair per call)
-    if (c->d_host_pos.cap < 3 * c->n * n_times) HIP_TRY(hipStreamSynchronize(c->s_main));
-    if (c->d_host_pos.ensure(3 * c->n * n_times) != AZ_OK) return AZ_ERR_HIP;
-    double *d_pos = c->d_host_pos.p;
-    int32_t rc = azh_propagate_device(c, times, n_times, offsets, d_pos, nullptr, AZ_OUT_TEME, 0.0, nullptr,
-                                      AZ_LAYOUT_TIME_MAJOR, 0, nullptr, nullptr);
-    // rows the propagator zero-filled (failed init, failed deep-space step) are skipped: a satellite
-    // is never at the geocentre, and two such rows must not be reported as a conjunction
-    if (rc == AZ_OK)
-        rc = coarse_screen(d_pos, c->n, n_times, AZ_LAYOUT_TIME_MAJOR, 0, threshold_km, nullptr, out_pairs, out_t,
-                           max_results, n_found, c->s_main, 1);
-    (void)hipStreamSynchronize(c->s_main);
-    return rc;
-}
 int32_t azh_screen_all_host(azh_constellation *c, const double *times, size_t n_times, const double *offsets,
                             double threshold_km, uint32_t *out_pairs, uint32_t *out_t, size_t max_results,
                             size_t *n_found)
 {
-    return guarded([&]() -> int32_t { return azh_screen_all_host_impl(c, times, n_times, offsets, threshold_km, out_pairs, out_t, max_results, n_found); });
+    return guarded([&]() -> int32_t {
+        if (!c || !n_found || (n_times && !times)) return AZ_ERR_NULL_POINTER;
+        *n_found = 0;
+        if (n_times == 0) return AZ_OK;
+        if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
+        // (the handle's grow-only result buffer: no 39-MB hipMalloc / hipFree pair per call)
+        if (c->d_host_pos.cap < 3 * c->n * n_times) HIP_TRY(hipStreamSynchronize(c->s_main));
+        if (c->d_host_pos.ensure(3 * c->n * n_times) != AZ_OK) return AZ_ERR_HIP;
+        double *d_pos = c->d_host_pos.p;
+        int32_t rc = azh_propagate_device(c, times, n_times, offsets, d_pos, nullptr, AZ_OUT_TEME, 0.0, nullptr,
+                                          AZ_LAYOUT_TIME_MAJOR, 0, nullptr, nullptr);
+        // rows the propagator zero-filled (failed init, failed deep-space step) are skipped: a satellite
+        // is never at the geocentre, and two such rows must not be reported as a conjunction
+        if (rc == AZ_OK)
+            rc = coarse_screen(d_pos, c->n, n_times, AZ_LAYOUT_TIME_MAJOR, 0, threshold_km, nullptr, out_pairs, out_t,
+                               max_results, n_found, c->s_main, 1);
+        (void)hipStreamSynchronize(c->s_main);
+        return rc;
+    });
 }
 
-static int32_t azh_propagate_host_impl(azh_constellation *c, const double *times, size_t n_times, const double *offsets,
-                           double *pos, double *vel, int32_t mode, double reference_jd, const uint8_t *mask,
-                           int32_t layout, size_t stride, uint8_t *err)
-{
-    if (!c || !pos || (n_times && !times)) return AZ_ERR_NULL_POINTER;
-    if (n_times == 0) return AZ_OK;
-    if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
-    if (stride == 0) stride = c->n;
-    const size_t rows = (layout == AZ_LAYOUT_TIME_MAJOR) ? stride : c->n;
-    const size_t bytes = rows * n_times * 3 * sizeof(double);
-    // device-side result buffers live in the handle and only ever grow: repeated calls (the Python propagate(),
-    // SatrecArray.sgp4) do not pay a hipMalloc/hipFree pair of hundreds of megabytes each time
-    const size_t words = bytes / sizeof(double);
-    // ONE satellite (BASELINE config 1: SatrecArray([sat]).sgp4(jd, fr)), TEME, no mask: (n_times, 1, 3) and (1, n_times, 3) are the
-    // same bytes as the one-satellite path's (n_times, 3), so the call IS azh_propagate_one_host on tsince = times + offset -- one
-    // kernel that reads its times from and writes into a pinned buffer, no staging of a grid, no increment / record / plan
-    // kernels: 30 us whether the grid repeats or not (through the constellation launch set: 49 us repeated, 109 us on a fresh grid)
-    // A FEW satellites x a few times (SatrecArray of a handful of records at one instant, a c_api client's tiny batch): the host
-    // route of the one-satellite calls, satellite by satellite (host_step.h; the table of a handle of <= 64 satellites is
-    // mirrored on the host) -- no staging, no launch, no synchronize.  Cost counted in near-earth points (a deep-space point = 2).
-    if (c->n > 1 && !c->h_el.empty() && mode == AZ_OUT_TEME && mask == nullptr && host_points() > 0) {
-        size_t cost = 0;
-        for (size_t sidx = 0; sidx < c->n; ++sidx) cost += n_times * ((c->h_flags[sidx] & AZ_FLAG_DEEP) ? 2 : 1);
-        if (cost <= host_points()) {
-            std::vector<double> ts(n_times), p(3 * n_times), v(3 * n_times);
-            std::vector<uint8_t> e(n_times);
-            for (size_t sidx = 0; sidx < c->n; ++sidx) {
-                const double o = offsets ? offsets[sidx] : 0.0;
-                for (size_t t = 0; t < n_times; ++t) ts[t] = times[t] + o;
-                azhost::propagate_points(c->h_el.data(), c->n_pad, sidx, c->h_flags[sidx], c->g, ts.data(), n_times, 0, nullptr, p.data(),
-                                         vel ? v.data() : nullptr, e.data());
-                for (size_t t = 0; t < n_times; ++t) {
-                    const size_t at = (layout == AZ_LAYOUT_TIME_MAJOR ? t * stride + sidx : sidx * n_times + t) * 3;
-                    memcpy(pos + at, &p[3 * t], 3 * sizeof(double));
-                    if (vel) memcpy(vel + at, &v[3 * t], 3 * sizeof(double));
-                    if (err) err[sidx * n_times + t] = e[t];
-                }
-            }
-            c->last_path = AZH_PATH_HOST_STEP;
-            c->cached_n_times = 0; // (nothing is staged on this route)
-            c->staged_valid = false;
-            c->timed = false;
-            return AZ_OK;
-        }
-    }
-    if (c->n == 1 && mode == AZ_OUT_TEME && mask == nullptr && (layout == AZ_LAYOUT_SAT_MAJOR || stride <= 1) && n_times <= kOneStage &&
-        AZ_FLAG_ERR(c->h_flags[0]) == 0) {
-        std::vector<double> ts(times, times + n_times);
-        if (offsets)
-            for (auto &t : ts) t += offsets[0];
-        c->last_path = 0; // (none of the constellation kernel families)
-        // nothing is staged on this route: the cached-input entry points must not find an older grid
-        c->cached_n_times = 0;
-        c->staged_valid = false;
-        c->timed = false;
-        return run_one_satellite(c, 0, ts.data(), n_times, 0, nullptr, pos, vel, err);
-    }
-    // A few satellites (what Satrec / SatrecArray([sat]) / a c_api client make): the kernels write straight into a pinned host
-    // buffer of the handle (device-addressable, coherent) and one synchronize ends the call -- three pageable device-to-host
-    // copies of a few KB cost ~15 us each.
-    const size_t err_bytes = err ? c->n * n_times : 0, small_total = bytes * (vel ? 2 : 1) + ((err_bytes + 63) & ~size_t(63));
-    if (small_total <= kSmallOut && mask == nullptr && !(layout == AZ_LAYOUT_TIME_MAJOR && stride > c->n)) {
-        if (c->h_small_cap < small_total) {
-            if (c->h_small) (void)hipHostFree(c->h_small);
-            c->h_small = nullptr;
-            c->h_small_cap = 0;
-            size_t cap = 65536;
-            while (cap < small_total) cap *= 2;
-            HIP_TRY(hipHostMalloc(&c->h_small, cap, hipHostMallocDefault));
-            c->h_small_cap = cap;
-        }
-        char *dev = nullptr;
-        HIP_TRY(hipHostGetDevicePointer((void **)&dev, c->h_small, 0));
-        const size_t o_vel = bytes, o_err = bytes * (vel ? 2 : 1);
-        int32_t rc = azh_propagate_device(c, times, n_times, offsets, reinterpret_cast<double *>(dev), vel ? reinterpret_cast<double *>(dev + o_vel) : nullptr,
-                                          mode, reference_jd, mask, layout, stride, err ? reinterpret_cast<uint8_t *>(dev + o_err) : nullptr, nullptr);
-        if (rc == AZ_OK && !hip_ok(hipStreamSynchronize(c->s_main), "sync")) rc = AZ_ERR_HIP;
-        if (rc != AZ_OK) {
-            (void)hipStreamSynchronize(c->s_main);
-            return rc;
-        }
-        const char *h = static_cast<const char *>(c->h_small);
-        memcpy(pos, h, bytes);
-        if (vel) memcpy(vel, h + o_vel, bytes);
-        if (err) memcpy(err, h + o_err, err_bytes);
-        return AZ_OK;
-    }
-    if (c->d_host_pos.ensure(words) != AZ_OK || (vel && c->d_host_vel.ensure(words) != AZ_OK) ||
-        (err && c->d_host_err.ensure(c->n * n_times) != AZ_OK))
-        return AZ_ERR_HIP;
-    double *d_pos = c->d_host_pos.p, *d_vel = vel ? c->d_host_vel.p : nullptr;
-    uint8_t *d_err = err ? c->d_host_err.p : nullptr;
-    int32_t rc = AZ_OK;
-    do {
-        // rows the kernels do not touch (masked satellites, stride padding) must come back unchanged
-        const bool partial = mask != nullptr || (layout == AZ_LAYOUT_TIME_MAJOR && stride > c->n);
-        if (partial) {
-            if (!hip_ok(hipMemcpyAsync(d_pos, pos, bytes, hipMemcpyHostToDevice, c->s_main), "H2D pos")) { rc = AZ_ERR_HIP; break; }
-            if (vel && !hip_ok(hipMemcpyAsync(d_vel, vel, bytes, hipMemcpyHostToDevice, c->s_main), "H2D vel")) { rc = AZ_ERR_HIP; break; }
-        }
-        rc = azh_propagate_device(c, times, n_times, offsets, d_pos, d_vel, mode, reference_jd, mask, layout, stride, d_err, nullptr);
-        if (rc != AZ_OK) break;
-        void *const dst[3] = {pos, vel, err};
-        const void *const src[3] = {d_pos, d_vel, d_err};
-        const size_t len[3] = {bytes, vel ? bytes : 0, err ? c->n * n_times : 0};
-        const unsigned thr = host_copy_threads();
-        // result arrays from azh_host_alloc are pinned: the DMA goes straight into them (no staging hop, no copy threads)
-        const bool pinned_out = host_pool().owns(pos, bytes) && (!vel || host_pool().owns(vel, bytes));
-        if (!pinned_out && thr > 0 && len[0] + len[1] + len[2] >= (size_t(8) << 20)) {
-            if ((rc = copy_back_staged(c->stager, dst, src, len, 3, c->s_main, thr)) != AZ_OK) break;
-        } else {
-            for (int k = 0; k < 3 && rc == AZ_OK; ++k)
-                if (len[k] && !hip_ok(hipMemcpyAsync(dst[k], src[k], len[k], hipMemcpyDeviceToHost, c->s_main), "D2H")) rc = AZ_ERR_HIP;
-            if (rc != AZ_OK) break;
-        }
-        if (!hip_ok(hipStreamSynchronize(c->s_main), "sync")) { rc = AZ_ERR_HIP; break; }
-    } while (0);
-    if (rc != AZ_OK) (void)hipStreamSynchronize(c->s_main);
-    return rc;
-}
 int32_t azh_propagate_host(azh_constellation *c, const double *times, size_t n_times, const double *offsets,
                            double *pos, double *vel, int32_t mode, double reference_jd, const uint8_t *mask,
                            int32_t layout, size_t stride, uint8_t *err)
 {
-    return guarded([&]() -> int32_t { return azh_propagate_host_impl(c, times, n_times, offsets, pos, vel, mode, reference_jd, mask, layout, stride, err); });
+    return guarded([&]() -> int32_t {
+        if (!c || !pos || (n_times && !times)) return AZ_ERR_NULL_POINTER;
+        if (n_times == 0) return AZ_OK;
+        if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
+        if (stride == 0) stride = c->n;
+        const size_t rows = (layout == AZ_LAYOUT_TIME_MAJOR) ? stride : c->n;
+        const size_t bytes = rows * n_times * 3 * sizeof(double);
+        // device-side result buffers live in the handle and only ever grow: repeated calls (the Python propagate(),
+        // SatrecArray.sgp4) do not pay a hipMalloc/hipFree pair of hundreds of megabytes each time
+        const size_t words = bytes / sizeof(double);
+        // ONE satellite (BASELINE config 1: SatrecArray([sat]).sgp4(jd, fr)), TEME, no mask: (n_times, 1, 3) and (1, n_times, 3) are the
+        // same bytes as the one-satellite path's (n_times, 3), so the call IS azh_propagate_one_host on tsince = times + offset -- one
+        // kernel that reads its times from and writes into a pinned buffer, no staging of a grid, no increment / record / plan
+        // kernels: 30 us whether the grid repeats or not (through the constellation launch set: 49 us repeated, 109 us on a fresh grid)
+        // A FEW satellites x a few times (SatrecArray of a handful of records at one instant, a c_api client's tiny batch): the host
+        // route of the one-satellite calls, satellite by satellite (host_step.h; the table of a handle of <= 64 satellites is
+        // mirrored on the host) -- no staging, no launch, no synchronize.  Cost counted in near-earth points (a deep-space point = 2).
+        if (c->n > 1 && !c->h_el.empty() && mode == AZ_OUT_TEME && mask == nullptr && host_points() > 0) {
+            size_t cost = 0;
+            for (size_t sidx = 0; sidx < c->n; ++sidx) cost += n_times * ((c->h_flags[sidx] & AZ_FLAG_DEEP) ? 2 : 1);
+            if (cost <= host_points()) {
+                std::vector<double> ts(n_times), p(3 * n_times), v(3 * n_times);
+                std::vector<uint8_t> e(n_times);
+                for (size_t sidx = 0; sidx < c->n; ++sidx) {
+                    const double o = offsets ? offsets[sidx] : 0.0;
+                    for (size_t t = 0; t < n_times; ++t) ts[t] = times[t] + o;
+                    azhost::propagate_points(c->h_el.data(), c->n_pad, sidx, c->h_flags[sidx], c->g, ts.data(), n_times, 0, nullptr, p.data(),
+                                             vel ? v.data() : nullptr, e.data());
+                    for (size_t t = 0; t < n_times; ++t) {
+                        const size_t at = (layout == AZ_LAYOUT_TIME_MAJOR ? t * stride + sidx : sidx * n_times + t) * 3;
+                        memcpy(pos + at, &p[3 * t], 3 * sizeof(double));
+                        if (vel) memcpy(vel + at, &v[3 * t], 3 * sizeof(double));
+                        if (err) err[sidx * n_times + t] = e[t];
+                    }
+                }
+                c->last_path = AZH_PATH_HOST_STEP;
+                c->cached_n_times = 0; // (nothing is staged on this route)
+                c->staged_valid = false;
+                c->timed = false;
+                return AZ_OK;
+            }
+        }
+        if (c->n == 1 && mode == AZ_OUT_TEME && mask == nullptr && (layout == AZ_LAYOUT_SAT_MAJOR || stride <= 1) && n_times <= kOneStage &&
+            AZ_FLAG_ERR(c->h_flags[0]) == 0) {
+            std::vector<double> ts(times, times + n_times);
+            if (offsets)
+                for (auto &t : ts) t += offsets[0];
+            c->last_path = 0; // (none of the constellation kernel families)
+            // nothing is staged on this route: the cached-input entry points must not find an older grid
+            c->cached_n_times = 0;
+            c->staged_valid = false;
+            c->timed = false;
+            return run_one_satellite(c, 0, ts.data(), n_times, 0, nullptr, pos, vel, err);
+        }
+        // A few satellites (what Satrec / SatrecArray([sat]) / a c_api client make): the kernels write straight into a pinned host
+        // buffer of the handle (device-addressable, coherent) and one synchronize ends the call -- three pageable device-to-host
+        // copies of a few KB cost ~15 us each.
+        const size_t err_bytes = err ? c->n * n_times : 0, small_total = bytes * (vel ? 2 : 1) + ((err_bytes + 63) & ~size_t(63));
+        if (small_total <= kSmallOut && mask == nullptr && !(layout == AZ_LAYOUT_TIME_MAJOR && stride > c->n)) {
+            if (c->h_small.ensure(small_total) != AZ_OK) return AZ_ERR_HIP;
+            char *dev = nullptr;
+            HIP_TRY(hipHostGetDevicePointer((void **)&dev, c->h_small.p, 0));
+            const size_t o_vel = bytes, o_err = bytes * (vel ? 2 : 1);
+            int32_t rc = azh_propagate_device(c, times, n_times, offsets, reinterpret_cast<double *>(dev), vel ? reinterpret_cast<double *>(dev + o_vel) : nullptr,
+                                              mode, reference_jd, mask, layout, stride, err ? reinterpret_cast<uint8_t *>(dev + o_err) : nullptr, nullptr);
+            if (rc == AZ_OK && !hip_ok(hipStreamSynchronize(c->s_main), "sync")) rc = AZ_ERR_HIP;
+            if (rc != AZ_OK) {
+                (void)hipStreamSynchronize(c->s_main);
+                return rc;
+            }
+            const char *h = static_cast<const char *>(c->h_small.p);
+            memcpy(pos, h, bytes);
+            if (vel) memcpy(vel, h + o_vel, bytes);
+            if (err) memcpy(err, h + o_err, err_bytes);
+            return AZ_OK;
+        }
+        if (c->d_host_pos.ensure(words) != AZ_OK || (vel && c->d_host_vel.ensure(words) != AZ_OK) ||
+            (err && c->d_host_err.ensure(c->n * n_times) != AZ_OK))
+            return AZ_ERR_HIP;
+        double *d_pos = c->d_host_pos.p, *d_vel = vel ? c->d_host_vel.p : nullptr;
+        uint8_t *d_err = err ? c->d_host_err.p : nullptr;
+        int32_t rc = AZ_OK;
+        do {
+            // rows the kernels do not touch (masked satellites, stride padding) must come back unchanged
+            const bool partial = mask != nullptr || (layout == AZ_LAYOUT_TIME_MAJOR && stride > c->n);
+            if (partial) {
+                if (!hip_ok(hipMemcpyAsync(d_pos, pos, bytes, hipMemcpyHostToDevice, c->s_main), "H2D pos")) { rc = AZ_ERR_HIP; break; }
+                if (vel && !hip_ok(hipMemcpyAsync(d_vel, vel, bytes, hipMemcpyHostToDevice, c->s_main), "H2D vel")) { rc = AZ_ERR_HIP; break; }
+            }
+            rc = azh_propagate_device(c, times, n_times, offsets, d_pos, d_vel, mode, reference_jd, mask, layout, stride, d_err, nullptr);
+            if (rc != AZ_OK) break;
+            void *const dst[3] = {pos, vel, err};
+            const void *const src[3] = {d_pos, d_vel, d_err};
+            const size_t len[3] = {bytes, vel ? bytes : 0, err ? c->n * n_times : 0};
+            const unsigned thr = host_copy_threads();
+            // result arrays from azh_host_alloc are pinned: the DMA goes straight into them (no staging hop, no copy threads)
+            const bool pinned_out = host_pool().owns(pos, bytes) && (!vel || host_pool().owns(vel, bytes));
+            if (!pinned_out && thr > 0 && len[0] + len[1] + len[2] >= (size_t(8) << 20)) {
+                if ((rc = copy_back_staged(c->stager, dst, src, len, 3, c->s_main, thr)) != AZ_OK) break;
+            } else {
+                for (int k = 0; k < 3 && rc == AZ_OK; ++k)
+                    if (len[k] && !hip_ok(hipMemcpyAsync(dst[k], src[k], len[k], hipMemcpyDeviceToHost, c->s_main), "D2H")) rc = AZ_ERR_HIP;
+                if (rc != AZ_OK) break;
+            }
+            if (!hip_ok(hipStreamSynchronize(c->s_main), "sync")) { rc = AZ_ERR_HIP; break; }
+        } while (0);
+        if (rc != AZ_OK) (void)hipStreamSynchronize(c->s_main);
+        return rc;
+    });
 }
 
-static int32_t azh_propagate_jd_host_impl(azh_constellation *c, const double *jd, const double *fr, size_t n_times, double *pos,
-                              double *vel, int32_t mode, int32_t layout, uint8_t *err)
-{
-    if (!c || !jd || !fr || !pos) return AZ_ERR_NULL_POINTER;
-    // Constellation.propagate (src/Constellation.zig L266-269): tsinceBase = (jd+fr - refEpoch)*1440,
-    // offsets = (refEpoch - epoch)*1440 (L153); GMST at jd+fr
-    // reference epoch: the first near-earth member's (Constellation.zig L139-140); a constellation without one
-    // uses its first member's
-    double ref = c->h_epoch.empty() ? 0.0 : c->h_epoch[0];
-    for (size_t s = 0; s < c->n; ++s)
-        if (AZ_FLAG_ERR(c->h_flags[s]) == 0 && !(c->h_flags[s] & AZ_FLAG_DEEP)) { ref = c->h_epoch[s]; break; }
-    std::vector<double> times(n_times), offs(c->n);
-    for (size_t t = 0; t < n_times; ++t) times[t] = ((jd[t] + fr[t]) - ref) * 1440.0;
-    for (size_t s = 0; s < c->n; ++s) offs[s] = (ref - c->h_epoch[s]) * 1440.0;
-    return azh_propagate_host(c, times.data(), n_times, offs.data(), pos, vel, mode, ref, nullptr, layout, 0, err);
-}
 int32_t azh_propagate_jd_host(azh_constellation *c, const double *jd, const double *fr, size_t n_times, double *pos,
                               double *vel, int32_t mode, int32_t layout, uint8_t *err)
 {
-    return guarded([&]() -> int32_t { return azh_propagate_jd_host_impl(c, jd, fr, n_times, pos, vel, mode, layout, err); });
+    return guarded([&]() -> int32_t {
+        if (!c || !jd || !fr || !pos) return AZ_ERR_NULL_POINTER;
+        // Constellation.propagate (src/Constellation.zig L266-269): tsinceBase = (jd+fr - refEpoch)*1440,
+        // offsets = (refEpoch - epoch)*1440 (L153); GMST at jd+fr
+        // reference epoch: the first near-earth member's (Constellation.zig L139-140); a constellation without one
+        // uses its first member's
+        double ref = c->h_epoch.empty() ? 0.0 : c->h_epoch[0];
+        for (size_t s = 0; s < c->n; ++s)
+            if (AZ_FLAG_ERR(c->h_flags[s]) == 0 && !(c->h_flags[s] & AZ_FLAG_DEEP)) { ref = c->h_epoch[s]; break; }
+        std::vector<double> times(n_times), offs(c->n);
+        for (size_t t = 0; t < n_times; ++t) times[t] = ((jd[t] + fr[t]) - ref) * 1440.0;
+        for (size_t s = 0; s < c->n; ++s) offs[s] = (ref - c->h_epoch[s]) * 1440.0;
+        return azh_propagate_host(c, times.data(), n_times, offs.data(), pos, vel, mode, ref, nullptr, layout, 0, err);
+    });
 }
 
 int32_t azh_synchronize(azh_constellation *c)
@@ -2725,40 +2654,34 @@ double azh_last_kernel_ms(azh_constellation *c)
     return (double)ms;
 }
 
-static int32_t azh_propagate_one_host_impl(azh_constellation *c, size_t sat, const double *tsince, size_t n, double *pos,
-                               double *vel, uint8_t *err)
-{
-    if (!c || !tsince || !pos) return AZ_ERR_NULL_POINTER;
-    if (sat >= c->n) return AZ_ERR_VALUE;
-    if (n == 0) return AZ_OK;
-    return run_one_satellite(c, sat, tsince, n, 0, nullptr, pos, vel, err);
-}
 int32_t azh_propagate_one_host(azh_constellation *c, size_t sat, const double *tsince, size_t n, double *pos,
                                double *vel, uint8_t *err)
 {
-    return guarded([&]() -> int32_t { return azh_propagate_one_host_impl(c, sat, tsince, n, pos, vel, err); });
+    return guarded([&]() -> int32_t {
+        if (!c || !tsince || !pos) return AZ_ERR_NULL_POINTER;
+        if (sat >= c->n) return AZ_ERR_VALUE;
+        if (n == 0) return AZ_OK;
+        return run_one_satellite(c, sat, tsince, n, 0, nullptr, pos, vel, err);
+    });
 }
 
-static int32_t azh_propagate_one_device_impl(azh_constellation *c, size_t sat, const double *d_tsince, size_t n, double *d_pos,
-                                 double *d_vel, uint8_t *d_err, void *stream)
-{
-    if (!c || !d_tsince || !d_pos) return AZ_ERR_NULL_POINTER;
-    if (sat >= c->n || n > 0xffffffffu) return AZ_ERR_VALUE;
-    if (n == 0) return AZ_OK;
-    if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
-    hipStream_t st = stream ? (hipStream_t)stream : c->s_main;
-    if (c->timing) HIP_TRY(hipEventRecord(c->ev_t0, st));
-    if (int32_t lrc = launch_one(c, sat, d_tsince, n, d_pos, d_vel, d_err, 0, st); lrc != AZ_OK) return lrc;
-    if (c->timing) {
-        HIP_TRY(hipEventRecord(c->ev_t1, st));
-        c->timed = true;
-    }
-    return AZ_OK;
-}
 int32_t azh_propagate_one_device(azh_constellation *c, size_t sat, const double *d_tsince, size_t n, double *d_pos,
                                  double *d_vel, uint8_t *d_err, void *stream)
 {
-    return guarded([&]() -> int32_t { return azh_propagate_one_device_impl(c, sat, d_tsince, n, d_pos, d_vel, d_err, stream); });
+    return guarded([&]() -> int32_t {
+        if (!c || !d_tsince || !d_pos) return AZ_ERR_NULL_POINTER;
+        if (sat >= c->n || n > 0xffffffffu) return AZ_ERR_VALUE;
+        if (n == 0) return AZ_OK;
+        if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
+        hipStream_t st = stream ? (hipStream_t)stream : c->s_main;
+        if (c->timing) HIP_TRY(hipEventRecord(c->ev_t0, st));
+        if (int32_t lrc = launch_one(c, sat, d_tsince, n, d_pos, d_vel, d_err, 0, st); lrc != AZ_OK) return lrc;
+        if (c->timing) {
+            HIP_TRY(hipEventRecord(c->ev_t1, st));
+            c->timed = true;
+        }
+        return AZ_OK;
+    });
 }
 
 // device-side known-answer hook for the element math of the kernels (devmath.h): out[0..n) sin, [n..2n) cos,
@@ -2768,18 +2691,14 @@ int32_t azh_selftest_math(const double *x, size_t n, double *out6n, int32_t devi
     if (!x || !out6n) return AZ_ERR_NULL_POINTER;
     if (n == 0) return AZ_OK;
     HIP_TRY(hipSetDevice(device));
-    double *d = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, sizeof(double) * 7 * n));
-    int32_t rc = AZ_OK;
-    if (!hip_ok(hipMemcpy(d, x, sizeof(double) * n, hipMemcpyHostToDevice), "H2D")) rc = AZ_ERR_HIP;
-    if (rc == AZ_OK) {
-        hipLaunchKernelGGL(k_math_kat, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, nullptr, d, (unsigned)n, d + n);
-        if (!hip_ok(hipGetLastError(), "k_math_kat") ||
-            !hip_ok(hipMemcpy(out6n, d + n, sizeof(double) * 6 * n, hipMemcpyDeviceToHost), "D2H"))
-            rc = AZ_ERR_HIP;
-    }
-    (void)hipFree(d);
-    return rc;
+    DevBuf<double> d;
+    if (d.ensure(7 * n) != AZ_OK) return AZ_ERR_HIP;
+    if (!hip_ok(hipMemcpy(d.p, x, sizeof(double) * n, hipMemcpyHostToDevice), "H2D")) return AZ_ERR_HIP;
+    hipLaunchKernelGGL(k_math_kat, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, nullptr, d.p, (unsigned)n, d.p + n);
+    if (!hip_ok(hipGetLastError(), "k_math_kat") ||
+        !hip_ok(hipMemcpy(out6n, d.p + n, sizeof(double) * 6 * n, hipMemcpyDeviceToHost), "D2H"))
+        return AZ_ERR_HIP;
+    return AZ_OK;
 }
 
 int32_t azh_selftest_host_step(const double *el, size_t n_pad, size_t sat, uint32_t flags, int32_t grav, const double *tsince_min,
@@ -2803,16 +2722,17 @@ struct azh_group {
     int n_dev = 0;
     size_t n = 0, rows = 0, n_chunks = 1;
     std::vector<int> devices;
-    std::vector<azh_constellation *> shard;
+    std::vector<std::unique_ptr<azh_constellation>> shard;
     std::vector<std::vector<uint32_t>> members; // catalog rows of every shard, ascending (== local order)
     std::vector<std::vector<double>> off_stage; // per-shard epoch offsets of the call in flight (source of an async H2D)
     std::vector<double> track_stage;            // the target's track of the group screen in flight (source of async H2Ds)
     std::vector<ncclComm_t> comms;              // created on the first all-gather
-    std::vector<hipStream_t> s_comm;
-    std::vector<hipEvent_t> ev;
+    std::vector<Stream> s_comm;
+    std::vector<Event> ev;
     size_t cell_lo(size_t chunk, int d) const { return std::min((chunk * n_dev + d) * rows, n); }
     size_t cell_hi(size_t chunk, int d) const { return std::min((chunk * n_dev + d) * rows + rows, n); }
     size_t padded() const { return n_chunks * n_dev * rows; }
+    ~azh_group(); // (the communicators, then every device's stream and event on that device; the shards release themselves)
 };
 
 namespace {
@@ -2854,19 +2774,22 @@ bool nccl_ok(ncclResult_t e, const char *what)
     return false;
 }
 
-void group_destroy(azh_group *g)
+} // namespace
+
+azh_group::~azh_group()
 {
-    if (!g) return;
-    for (size_t d = 0; d < g->comms.size(); ++d)
-        if (g->comms[d]) (void)rccl().CommDestroy(g->comms[d]);
-    for (int d = 0; d < (int)g->s_comm.size(); ++d) {
-        (void)hipSetDevice(g->devices[d]);
-        if (g->s_comm[d]) (void)hipStreamDestroy(g->s_comm[d]);
-        if (d < (int)g->ev.size() && g->ev[d]) (void)hipEventDestroy(g->ev[d]);
+    for (ncclComm_t comm : comms)
+        if (comm) (void)rccl().CommDestroy(comm);
+    for (size_t d = 0; d < s_comm.size(); ++d) {
+        (void)hipSetDevice(devices[d]);
+        s_comm[d].reset();
+        ev[d].reset();
     }
-    for (azh_constellation *c : g->shard) destroy(c);
-    delete g;
 }
+
+namespace {
+
+void group_destroy(azh_group *g) { delete g; }
 
 int32_t group_build(const std::vector<azh::TleRecord> &recs, int grav, const int32_t *devices, int32_t n_devices,
                     int32_t n_chunks, azh_group **out)
@@ -2874,7 +2797,7 @@ int32_t group_build(const std::vector<azh::TleRecord> &recs, int grav, const int
     if (!devices || !out) return AZ_ERR_NULL_POINTER;
     *out = nullptr;
     if (n_devices < 1 || n_chunks < 1 || recs.empty()) return AZ_ERR_VALUE;
-    azh_group *g = new (std::nothrow) azh_group();
+    std::unique_ptr<azh_group> g(new (std::nothrow) azh_group());
     if (!g) return AZ_ERR_ALLOC_FAILED;
     g->n_dev = n_devices;
     g->n = recs.size();
@@ -2883,11 +2806,10 @@ int32_t group_build(const std::vector<azh::TleRecord> &recs, int grav, const int
     const size_t cells = (size_t)n_devices * (size_t)n_chunks;
     g->rows = ((g->n + cells - 1) / cells + 63) / 64 * 64;
     g->n_chunks = std::max<size_t>(1, std::min<size_t>((size_t)n_chunks, (g->n + n_devices * g->rows - 1) / (n_devices * g->rows)));
-    g->shard.assign(n_devices, nullptr);
+    g->shard.resize(n_devices);
     g->members.resize(n_devices);
     g->off_stage.resize(n_devices);
-    int32_t rc = AZ_OK;
-    for (int d = 0; d < n_devices && rc == AZ_OK; ++d) {
+    for (int d = 0; d < n_devices; ++d) {
         std::vector<azh::TleRecord> mine;
         for (size_t c = 0; c < g->n_chunks; ++c)
             for (size_t r = g->cell_lo(c, d); r < g->cell_hi(c, d); ++r) {
@@ -2895,13 +2817,11 @@ int32_t group_build(const std::vector<azh::TleRecord> &recs, int grav, const int
                 g->members[d].push_back((uint32_t)r);
             }
         if (mine.empty()) continue; // more devices than 64-satellite cells
-        rc = build_from_records(mine, grav, devices[d], &g->shard[d]);
+        azh_constellation *c = nullptr;
+        if (int32_t rc = build_from_records(mine, grav, devices[d], &c); rc != AZ_OK) return rc;
+        g->shard[d].reset(c);
     }
-    if (rc != AZ_OK) {
-        group_destroy(g);
-        return rc;
-    }
-    *out = g;
+    *out = g.release();
     return AZ_OK;
 }
 
@@ -2909,7 +2829,7 @@ int32_t group_build(const std::vector<azh::TleRecord> &recs, int grav, const int
 int32_t group_stage(azh_group *g, int d, const double *times, size_t n_times, const double *offsets, int32_t mode,
                     double reference_jd, bool want_vel, bool want_err)
 {
-    azh_constellation *c = g->shard[d];
+    azh_constellation *c = g->shard[d].get();
     if (!c) return AZ_OK;
     if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
     std::vector<double> &off = g->off_stage[d]; // outlives the asynchronous upload (the callers synchronise before returning)
@@ -2965,167 +2885,161 @@ int32_t azh_group_get_epochs(const azh_group *g, double *out)
     return AZ_OK;
 }
 
-static int32_t azh_group_propagate_host_impl(azh_group *g, const double *times, size_t n_times, const double *offsets, size_t n_offsets,
-                                 double *pos, double *vel, int32_t mode, double reference_jd, uint8_t *err)
-{
-    if (!g || !pos || (n_times && !times)) return AZ_ERR_NULL_POINTER;
-    if (mode < 0 || mode > 2 || (offsets && n_offsets < g->n)) return AZ_ERR_VALUE;
-    if (n_times == 0) return AZ_OK;
-    const size_t row = n_times * 3;
-    int32_t rc = AZ_OK;
-    // enqueue everything on every device first (asynchronous), then wait: the devices run side by side
-    for (int d = 0; d < g->n_dev && rc == AZ_OK; ++d) {
-        azh_constellation *c = g->shard[d];
-        if (!c) continue;
-        if ((rc = group_stage(g, d, times, n_times, offsets, mode, reference_jd, vel != nullptr, err != nullptr)) != AZ_OK) break;
-        rc = launch_all(c, c->d_host_pos.p, vel ? c->d_host_vel.p : nullptr, AZ_LAYOUT_SAT_MAJOR, 0,
-                        err ? c->d_host_err.p : nullptr, c->s_main);
-        if (rc != AZ_OK) break;
-    }
-    // Copies: a cell = consecutive catalog rows = consecutive local rows, one copy per cell and array.  Every device gets its
-    // OWN copier thread, which stages its cells through that device's pinned slots while its share of the host copy threads
-    // moves each landed chunk into the caller's array (copy_back_staged): the N PCIe links run side by side (issued from one
-    // thread, host-synchronous pageable copies would take turns) and at least N threads write the host arrays.
-    if (rc == AZ_OK) {
-        std::vector<int32_t> rcs(g->n_dev, AZ_OK);
-        const size_t arr_bytes = g->n * row * sizeof(double);
-        // (result arrays from azh_host_alloc are pinned: every device's DMA goes straight into them)
-        const bool staged = host_copy_threads() > 0 && !(host_pool().owns(pos, arr_bytes) && (!vel || host_pool().owns(vel, arr_bytes)));
-        const unsigned per_dev = std::max(1u, host_copy_threads() / (unsigned)std::max(1, g->n_dev)); // host threads behind each device
-        auto copy_cells = [&](int d) {
-            azh_constellation *c = g->shard[d];
-            if (!c) return;
-            if (hipSetDevice(c->device) != hipSuccess) { rcs[d] = AZ_ERR_HIP; return; }
-            std::vector<void *> dst;
-            std::vector<const void *> src;
-            std::vector<size_t> len;
-            for (int arr = 0; arr < 3; ++arr) {
-                if ((arr == 1 && !vel) || (arr == 2 && !err)) continue;
-                const size_t unit = arr == 2 ? n_times : row * sizeof(double); // bytes per satellite row
-                const char *base = arr == 0 ? (const char *)c->d_host_pos.p : arr == 1 ? (const char *)c->d_host_vel.p : (const char *)c->d_host_err.p;
-                char *out = arr == 0 ? (char *)pos : arr == 1 ? (char *)vel : (char *)err;
-                size_t local = 0;
-                for (size_t k = 0; k < g->n_chunks; ++k) {
-                    const size_t lo = g->cell_lo(k, d), cnt = g->cell_hi(k, d) - lo;
-                    if (!cnt) continue;
-                    dst.push_back(out + lo * unit); src.push_back(base + local * unit); len.push_back(cnt * unit);
-                    local += cnt;
-                }
-            }
-            if (staged) {
-                rcs[d] = copy_back_staged(c->stager, dst.data(), src.data(), len.data(), (int)dst.size(), c->s_main, per_dev);
-            } else {
-                for (size_t k = 0; k < dst.size(); ++k)
-                    if (hipMemcpyAsync(dst[k], src[k], len[k], hipMemcpyDeviceToHost, c->s_main) != hipSuccess) { rcs[d] = AZ_ERR_HIP; return; }
-            }
-            if (hipStreamSynchronize(c->s_main) != hipSuccess) rcs[d] = AZ_ERR_HIP;
-        };
-        // (it runs in std::thread: an exception that left it -- a vector growing out of memory -- would be std::terminate)
-        auto copier = [&](int d) {
-            try {
-                copy_cells(d);
-            } catch (const std::bad_alloc &) {
-                rcs[d] = AZ_ERR_ALLOC_FAILED;
-            } catch (...) {
-                rcs[d] = AZ_ERR_UNKNOWN;
-            }
-        };
-        std::vector<std::thread> th;
-        for (int d = 1; d < g->n_dev; ++d) {
-            try {
-                th.emplace_back(copier, d);
-            } catch (const std::system_error &) {
-                copier(d);
-            }
-        }
-        copier(0);
-        for (auto &t : th) t.join();
-        for (int d = 0; d < g->n_dev; ++d)
-            if (rcs[d] != AZ_OK) { rc = rcs[d]; if (g_last_error.empty()) g_last_error = "device-to-host copy failed"; (void)hipGetLastError(); }
-    }
-    for (int d = 0; d < g->n_dev; ++d) {
-        azh_constellation *c = g->shard[d];
-        if (!c) continue;
-        if (set_device(c) != AZ_OK || !hip_ok(hipStreamSynchronize(c->s_main), "sync") || !hip_ok(hipStreamSynchronize(c->s_deep), "sync"))
-            rc = rc == AZ_OK ? AZ_ERR_HIP : rc;
-    }
-    return rc;
-}
 int32_t azh_group_propagate_host(azh_group *g, const double *times, size_t n_times, const double *offsets, size_t n_offsets,
                                  double *pos, double *vel, int32_t mode, double reference_jd, uint8_t *err)
 {
-    return guarded([&]() -> int32_t { return azh_group_propagate_host_impl(g, times, n_times, offsets, n_offsets, pos, vel, mode, reference_jd, err); });
+    return guarded([&]() -> int32_t {
+        if (!g || !pos || (n_times && !times)) return AZ_ERR_NULL_POINTER;
+        if (mode < 0 || mode > 2 || (offsets && n_offsets < g->n)) return AZ_ERR_VALUE;
+        if (n_times == 0) return AZ_OK;
+        const size_t row = n_times * 3;
+        int32_t rc = AZ_OK;
+        // enqueue everything on every device first (asynchronous), then wait: the devices run side by side
+        for (int d = 0; d < g->n_dev && rc == AZ_OK; ++d) {
+            azh_constellation *c = g->shard[d].get();
+            if (!c) continue;
+            if ((rc = group_stage(g, d, times, n_times, offsets, mode, reference_jd, vel != nullptr, err != nullptr)) != AZ_OK) break;
+            rc = launch_all(c, c->d_host_pos.p, vel ? c->d_host_vel.p : nullptr, AZ_LAYOUT_SAT_MAJOR, 0,
+                            err ? c->d_host_err.p : nullptr, c->s_main);
+            if (rc != AZ_OK) break;
+        }
+        // Copies: a cell = consecutive catalog rows = consecutive local rows, one copy per cell and array.  Every device gets its
+        // OWN copier thread, which stages its cells through that device's pinned slots while its share of the host copy threads
+        // moves each landed chunk into the caller's array (copy_back_staged): the N PCIe links run side by side (issued from one
+        // thread, host-synchronous pageable copies would take turns) and at least N threads write the host arrays.
+        if (rc == AZ_OK) {
+            std::vector<int32_t> rcs(g->n_dev, AZ_OK);
+            const size_t arr_bytes = g->n * row * sizeof(double);
+            // (result arrays from azh_host_alloc are pinned: every device's DMA goes straight into them)
+            const bool staged = host_copy_threads() > 0 && !(host_pool().owns(pos, arr_bytes) && (!vel || host_pool().owns(vel, arr_bytes)));
+            const unsigned per_dev = std::max(1u, host_copy_threads() / (unsigned)std::max(1, g->n_dev)); // host threads behind each device
+            auto copy_cells = [&](int d) {
+                azh_constellation *c = g->shard[d].get();
+                if (!c) return;
+                if (hipSetDevice(c->device) != hipSuccess) { rcs[d] = AZ_ERR_HIP; return; }
+                std::vector<void *> dst;
+                std::vector<const void *> src;
+                std::vector<size_t> len;
+                for (int arr = 0; arr < 3; ++arr) {
+                    if ((arr == 1 && !vel) || (arr == 2 && !err)) continue;
+                    const size_t unit = arr == 2 ? n_times : row * sizeof(double); // bytes per satellite row
+                    const char *base = arr == 0 ? (const char *)c->d_host_pos.p : arr == 1 ? (const char *)c->d_host_vel.p : (const char *)c->d_host_err.p;
+                    char *out = arr == 0 ? (char *)pos : arr == 1 ? (char *)vel : (char *)err;
+                    size_t local = 0;
+                    for (size_t k = 0; k < g->n_chunks; ++k) {
+                        const size_t lo = g->cell_lo(k, d), cnt = g->cell_hi(k, d) - lo;
+                        if (!cnt) continue;
+                        dst.push_back(out + lo * unit); src.push_back(base + local * unit); len.push_back(cnt * unit);
+                        local += cnt;
+                    }
+                }
+                if (staged) {
+                    rcs[d] = copy_back_staged(c->stager, dst.data(), src.data(), len.data(), (int)dst.size(), c->s_main, per_dev);
+                } else {
+                    for (size_t k = 0; k < dst.size(); ++k)
+                        if (hipMemcpyAsync(dst[k], src[k], len[k], hipMemcpyDeviceToHost, c->s_main) != hipSuccess) { rcs[d] = AZ_ERR_HIP; return; }
+                }
+                if (hipStreamSynchronize(c->s_main) != hipSuccess) rcs[d] = AZ_ERR_HIP;
+            };
+            // (it runs in std::thread: an exception that left it -- a vector growing out of memory -- would be std::terminate)
+            auto copier = [&](int d) {
+                try {
+                    copy_cells(d);
+                } catch (const std::bad_alloc &) {
+                    rcs[d] = AZ_ERR_ALLOC_FAILED;
+                } catch (...) {
+                    rcs[d] = AZ_ERR_UNKNOWN;
+                }
+            };
+            std::vector<std::thread> th;
+            for (int d = 1; d < g->n_dev; ++d) {
+                try {
+                    th.emplace_back(copier, d);
+                } catch (const std::system_error &) {
+                    copier(d);
+                }
+            }
+            copier(0);
+            for (auto &t : th) t.join();
+            for (int d = 0; d < g->n_dev; ++d)
+                if (rcs[d] != AZ_OK) { rc = rcs[d]; if (g_last_error.empty()) g_last_error = "device-to-host copy failed"; (void)hipGetLastError(); }
+        }
+        for (int d = 0; d < g->n_dev; ++d) {
+            azh_constellation *c = g->shard[d].get();
+            if (!c) continue;
+            if (set_device(c) != AZ_OK || !hip_ok(hipStreamSynchronize(c->s_main), "sync") || !hip_ok(hipStreamSynchronize(c->s_deep), "sync"))
+                rc = rc == AZ_OK ? AZ_ERR_HIP : rc;
+        }
+        return rc;
+    });
 }
 
-static int32_t azh_group_propagate_allgather_impl(azh_group *g, const double *times, size_t n_times, const double *offsets, size_t n_offsets,
-                                      double *const *d_pos, double *const *d_vel)
-{
-    if (!g || !d_pos || (n_times && !times)) return AZ_ERR_NULL_POINTER;
-    if (offsets && n_offsets < g->n) return AZ_ERR_VALUE;
-    if (n_times == 0) return AZ_OK;
-    for (int d = 0; d < g->n_dev; ++d)
-        if (!g->shard[d]) { g_last_error = "more devices than 64-satellite cells"; return AZ_ERR_VALUE; }
-    Rccl &R = rccl();
-    if (!R.ok) { g_last_error = "librccl.so could not be loaded"; return AZ_ERR_HIP; }
-    if (g->comms.empty()) {
-        g->comms.assign(g->n_dev, nullptr);
-        if (!nccl_ok(R.CommInitAll(g->comms.data(), g->n_dev, g->devices.data()), "ncclCommInitAll")) { g->comms.clear(); return AZ_ERR_HIP; }
-        g->s_comm.assign(g->n_dev, nullptr);
-        g->ev.assign(g->n_dev, nullptr);
-        for (int d = 0; d < g->n_dev; ++d) {
-            HIP_TRY(hipSetDevice(g->devices[d]));
-            HIP_TRY(hipStreamCreateWithFlags(&g->s_comm[d], hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&g->ev[d], hipEventDisableTiming));
-        }
-    }
-    const size_t row = n_times * 3, cell = g->rows * row;
-    int32_t rc = AZ_OK;
-    for (int d = 0; d < g->n_dev && rc == AZ_OK; ++d)
-        rc = group_stage(g, d, times, n_times, offsets, AZ_OUT_TEME, 0.0, d_vel != nullptr, false);
-    // chunk pipeline: chunk k is propagated on every device's own stream; its all-gather runs on the communication
-    // streams while chunk k+1 is being propagated
-    for (size_t k = 0; k < g->n_chunks && rc == AZ_OK; ++k) {
-        for (int d = 0; d < g->n_dev && rc == AZ_OK; ++d) {
-            azh_constellation *c = g->shard[d];
-            if (set_device(c) != AZ_OK) { rc = AZ_ERR_HIP; break; }
-            const size_t cnt = g->cell_hi(k, d) - g->cell_lo(k, d);
-            if (cnt < g->rows) {
-                // a partial (or empty) cell: the all-gather still moves `rows` rows of it -- its padding rows are zeros,
-                // not whatever an earlier call left in the grow-only buffers
-                const size_t at = (k * g->rows + cnt) * row, len = (g->rows - cnt) * row * sizeof(double);
-                if (!hip_ok(hipMemsetAsync(c->d_host_pos.p + at, 0, len, c->s_main), "memset pad") ||
-                    (d_vel && !hip_ok(hipMemsetAsync(c->d_host_vel.p + at, 0, len, c->s_main), "memset pad"))) { rc = AZ_ERR_HIP; break; }
-            }
-            if (cnt) rc = launch_all(c, c->d_host_pos.p, d_vel ? c->d_host_vel.p : nullptr, AZ_LAYOUT_SAT_MAJOR, 0, nullptr,
-                                     c->s_main, 0, k * g->rows, k * g->rows + cnt);
-            if (rc != AZ_OK) break;
-            if (!hip_ok(hipEventRecord(g->ev[d], c->s_main), "record") || !hip_ok(hipStreamWaitEvent(g->s_comm[d], g->ev[d], 0), "wait"))
-                rc = AZ_ERR_HIP;
-        }
-        if (rc != AZ_OK) break;
-        for (int arr = 0; arr < (d_vel ? 2 : 1) && rc == AZ_OK; ++arr) {
-            if (!nccl_ok(R.GroupStart(), "ncclGroupStart")) { rc = AZ_ERR_HIP; break; }
-            for (int d = 0; d < g->n_dev; ++d) {
-                azh_constellation *c = g->shard[d];
-                const double *src = (arr ? c->d_host_vel.p : c->d_host_pos.p) + k * cell;
-                double *dst = (arr ? d_vel[d] : d_pos[d]) + k * g->n_dev * cell;
-                if (!nccl_ok(R.AllGather(src, dst, cell, ncclDouble, g->comms[d], g->s_comm[d]), "ncclAllGather")) rc = AZ_ERR_HIP;
-            }
-            if (!nccl_ok(R.GroupEnd(), "ncclGroupEnd")) rc = AZ_ERR_HIP;
-        }
-    }
-    for (int d = 0; d < g->n_dev; ++d) {
-        azh_constellation *c = g->shard[d];
-        if (set_device(c) != AZ_OK || !hip_ok(hipStreamSynchronize(c->s_main), "sync") || !hip_ok(hipStreamSynchronize(c->s_deep), "sync") ||
-            !hip_ok(hipStreamSynchronize(g->s_comm[d]), "sync"))
-            rc = rc == AZ_OK ? AZ_ERR_HIP : rc;
-    }
-    return rc;
-}
 int32_t azh_group_propagate_allgather(azh_group *g, const double *times, size_t n_times, const double *offsets, size_t n_offsets,
                                       double *const *d_pos, double *const *d_vel)
 {
-    return guarded([&]() -> int32_t { return azh_group_propagate_allgather_impl(g, times, n_times, offsets, n_offsets, d_pos, d_vel); });
+    return guarded([&]() -> int32_t {
+        if (!g || !d_pos || (n_times && !times)) return AZ_ERR_NULL_POINTER;
+        if (offsets && n_offsets < g->n) return AZ_ERR_VALUE;
+        if (n_times == 0) return AZ_OK;
+        for (int d = 0; d < g->n_dev; ++d)
+            if (!g->shard[d]) { g_last_error = "more devices than 64-satellite cells"; return AZ_ERR_VALUE; }
+        Rccl &R = rccl();
+        if (!R.ok) { g_last_error = "librccl.so could not be loaded"; return AZ_ERR_HIP; }
+        if (g->comms.empty()) {
+            g->comms.assign(g->n_dev, nullptr);
+            if (!nccl_ok(R.CommInitAll(g->comms.data(), g->n_dev, g->devices.data()), "ncclCommInitAll")) { g->comms.clear(); return AZ_ERR_HIP; }
+            g->s_comm.resize(g->n_dev);
+            g->ev.resize(g->n_dev);
+            for (int d = 0; d < g->n_dev; ++d) {
+                HIP_TRY(hipSetDevice(g->devices[d]));
+                HIP_TRY(g->s_comm[d].create(hipStreamNonBlocking));
+                HIP_TRY(g->ev[d].create(hipEventDisableTiming));
+            }
+        }
+        const size_t row = n_times * 3, cell = g->rows * row;
+        int32_t rc = AZ_OK;
+        for (int d = 0; d < g->n_dev && rc == AZ_OK; ++d)
+            rc = group_stage(g, d, times, n_times, offsets, AZ_OUT_TEME, 0.0, d_vel != nullptr, false);
+        // chunk pipeline: chunk k is propagated on every device's own stream; its all-gather runs on the communication
+        // streams while chunk k+1 is being propagated
+        for (size_t k = 0; k < g->n_chunks && rc == AZ_OK; ++k) {
+            for (int d = 0; d < g->n_dev && rc == AZ_OK; ++d) {
+                azh_constellation *c = g->shard[d].get();
+                if (set_device(c) != AZ_OK) { rc = AZ_ERR_HIP; break; }
+                const size_t cnt = g->cell_hi(k, d) - g->cell_lo(k, d);
+                if (cnt < g->rows) {
+                    // a partial (or empty) cell: the all-gather still moves `rows` rows of it -- its padding rows are zeros,
+                    // not whatever an earlier call left in the grow-only buffers
+                    const size_t at = (k * g->rows + cnt) * row, len = (g->rows - cnt) * row * sizeof(double);
+                    if (!hip_ok(hipMemsetAsync(c->d_host_pos.p + at, 0, len, c->s_main), "memset pad") ||
+                        (d_vel && !hip_ok(hipMemsetAsync(c->d_host_vel.p + at, 0, len, c->s_main), "memset pad"))) { rc = AZ_ERR_HIP; break; }
+                }
+                if (cnt) rc = launch_all(c, c->d_host_pos.p, d_vel ? c->d_host_vel.p : nullptr, AZ_LAYOUT_SAT_MAJOR, 0, nullptr,
+                                         c->s_main, 0, k * g->rows, k * g->rows + cnt);
+                if (rc != AZ_OK) break;
+                if (!hip_ok(hipEventRecord(g->ev[d], c->s_main), "record") || !hip_ok(hipStreamWaitEvent(g->s_comm[d], g->ev[d], 0), "wait"))
+                    rc = AZ_ERR_HIP;
+            }
+            if (rc != AZ_OK) break;
+            for (int arr = 0; arr < (d_vel ? 2 : 1) && rc == AZ_OK; ++arr) {
+                if (!nccl_ok(R.GroupStart(), "ncclGroupStart")) { rc = AZ_ERR_HIP; break; }
+                for (int d = 0; d < g->n_dev; ++d) {
+                    azh_constellation *c = g->shard[d].get();
+                    const double *src = (arr ? c->d_host_vel.p : c->d_host_pos.p) + k * cell;
+                    double *dst = (arr ? d_vel[d] : d_pos[d]) + k * g->n_dev * cell;
+                    if (!nccl_ok(R.AllGather(src, dst, cell, ncclDouble, g->comms[d], g->s_comm[d]), "ncclAllGather")) rc = AZ_ERR_HIP;
+                }
+                if (!nccl_ok(R.GroupEnd(), "ncclGroupEnd")) rc = AZ_ERR_HIP;
+            }
+        }
+        for (int d = 0; d < g->n_dev; ++d) {
+            azh_constellation *c = g->shard[d].get();
+            if (set_device(c) != AZ_OK || !hip_ok(hipStreamSynchronize(c->s_main), "sync") || !hip_ok(hipStreamSynchronize(c->s_deep), "sync") ||
+                !hip_ok(hipStreamSynchronize(g->s_comm[d]), "sync"))
+                rc = rc == AZ_OK ? AZ_ERR_HIP : rc;
+        }
+        return rc;
+    });
 }
 
 // The sharded consumer ("a consumer that only needs its own shard"): the fused single-target screen
@@ -3150,7 +3064,7 @@ int32_t group_screen(azh_group *g, const double *times, size_t n_times, const do
     if (owner < 0) return AZ_ERR_VALUE;
     int32_t rc = AZ_OK;
     auto shard_offsets = [&](int d) -> const double * {
-        azh_constellation *c = g->shard[d];
+        azh_constellation *c = g->shard[d].get();
         if (!offsets || !c) return nullptr;
         std::vector<double> &off = g->off_stage[d];
         off.resize(c->n);
@@ -3161,11 +3075,11 @@ int32_t group_screen(azh_group *g, const double *times, size_t n_times, const do
     std::vector<double> &track = g->track_stage;
     const unsigned nt = (unsigned)n_times;
     if (nt > 0 && g->n_dev > 1) {
-        azh_constellation *c = g->shard[owner];
+        azh_constellation *c = g->shard[owner].get();
         if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
         if ((rc = stage_inputs(c, times, n_times, shard_offsets(owner), nullptr, AZ_OUT_TEME, 0.0, c->s_main)) != AZ_OK) return rc;
         if (c->d_tgt.ensure((size_t)nt * 3) != AZ_OK) return AZ_ERR_HIP;
-        hipLaunchKernelGGL((k_one_satellite<false>), dim3((nt + 63) / 64), dim3(64), 0, c->s_main, c->d_el, c->d_flags, c->n_pad,
+        hipLaunchKernelGGL((k_one_satellite<false>), dim3((nt + 63) / 64), dim3(64), 0, c->s_main, c->d_el.p, c->d_flags.p, c->n_pad,
                            (unsigned)t_local, c->d_times.p, nt, c->d_tgt.p, (double *)nullptr, (unsigned char *)nullptr, 0, c->g,
                            c->have_offsets ? c->d_offsets.p : (const double *)nullptr, 1);
         HIP_TRY(hipGetLastError());
@@ -3180,7 +3094,7 @@ int32_t group_screen(azh_group *g, const double *times, size_t n_times, const do
     std::vector<int32_t> rcs(g->n_dev, AZ_OK);
     for (int d = 0; d < g->n_dev; ++d) (void)shard_offsets(d); // (fills g->off_stage[d] on this thread: no allocation races below)
     auto work = [&](int d) -> int32_t {
-        azh_constellation *c = g->shard[d];
+        azh_constellation *c = g->shard[d].get();
         if (!c) return AZ_OK;
         if (hipSetDevice(c->device) != hipSuccess) return AZ_ERR_HIP;
         double *out_d = d_min_dist ? d_min_dist[d] : nullptr;
@@ -3244,7 +3158,7 @@ int32_t group_screen(azh_group *g, const double *times, size_t n_times, const do
         if (g_last_error.empty()) g_last_error = "sharded screen failed on a device";
         (void)hipGetLastError();
         for (int d = 0; d < g->n_dev; ++d) {
-            azh_constellation *c = g->shard[d];
+            azh_constellation *c = g->shard[d].get();
             if (c && set_device(c) == AZ_OK) (void)hipStreamSynchronize(c->s_main);
         }
     }
@@ -3287,7 +3201,7 @@ int32_t azh_group_synchronize(azh_group *g)
     if (!g) return AZ_ERR_NULL_POINTER;
     int32_t rc = AZ_OK;
     for (int d = 0; d < g->n_dev; ++d) {
-        azh_constellation *c = g->shard[d];
+        azh_constellation *c = g->shard[d].get();
         if (!c) continue;
         if (set_device(c) != AZ_OK || !hip_ok(hipStreamSynchronize(c->s_main), "sync") || !hip_ok(hipStreamSynchronize(c->s_deep), "sync") ||
             !hip_ok(hipStreamSynchronize(c->s_ecc), "sync"))
@@ -3348,12 +3262,12 @@ int32_t sgp4_init(void *tle, int32_t grav, void **out)
     else if (f & AZ_FLAG_DEEP)
         e = AZ_ERR_DEEP_SPACE_NOT_SUPPORTED;
     if (e != AZ_OK) {
-        destroy(c);
+        delete c;
         return e;
     }
     Sgp4Handle *h = new (std::nothrow) Sgp4Handle{c};
     if (!h) {
-        destroy(c);
+        delete c;
         return AZ_ERR_ALLOC_FAILED;
     }
     *out = h;
@@ -3363,7 +3277,7 @@ int32_t sgp4_init(void *tle, int32_t grav, void **out)
 void sgp4_free(void *h)
 {
     if (!h) return;
-    destroy(static_cast<Sgp4Handle *>(h)->c);
+    delete static_cast<Sgp4Handle *>(h)->c;
     delete static_cast<Sgp4Handle *>(h);
 }
 
