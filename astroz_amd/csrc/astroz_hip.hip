@@ -20,6 +20,7 @@
 #include <memory>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "kernels.h"
@@ -517,23 +518,60 @@ unsigned auto_tile(unsigned n_list, unsigned n_times, unsigned forced, unsigned 
     return std::max(tile, 1u);
 }
 
-template <bool DEEP, bool FRAME>
-void launch_propagate2(const PropArgs &a, int layout, bool vel, hipStream_t st)
+// launch shapes: grid.x padded to a multiple of 8 (XCD-aware placement, see k_propagate); grid.y = time segments of `tile`
+inline unsigned pad8(unsigned n) { return (n + 7) / 8 * 8; }
+inline unsigned cgrid_y(unsigned n_times, unsigned tile) { return (n_times + tile - 1) / tile; }
+
+// Runtime choices -> template arguments.  Each helper calls f with std::integral_constant values, which a generic lambda passes
+// on as template arguments, so that every kernel family picks its template arguments in one place.  The helpers offer only
+// combinations that some launch asks for (the screen sink: TEME, no velocities), so that no kernel is instantiated that is
+// never launched; a family with fewer forms maps the values onto its own (k_tiles_fast / k_cols_fast: no tight DELTA form).
+template <int V>
+using int_c = std::integral_constant<int, V>;
+template <class F>
+void with_bool(bool b, F &&f)
 {
-    // grid.x padded to a multiple of 8: XCD-aware placement (see k_propagate)
-    dim3 grid(((a.n_list + AZ_BLOCK - 1) / AZ_BLOCK + 7) / 8 * 8, (a.n_times + a.tile - 1) / a.tile);
-    dim3 block(AZ_BLOCK);
-    if (layout == AZ_LAYOUT_TIME_MAJOR) {
-        if (vel)
-            hipLaunchKernelGGL((k_propagate<1, true, DEEP, FRAME>), grid, block, 0, st, a);
-        else
-            hipLaunchKernelGGL((k_propagate<1, false, DEEP, FRAME>), grid, block, 0, st, a);
-    } else {
-        if (vel)
-            hipLaunchKernelGGL((k_propagate<0, true, DEEP, FRAME>), grid, block, 0, st, a);
-        else
-            hipLaunchKernelGGL((k_propagate<0, false, DEEP, FRAME>), grid, block, 0, st, a);
-    }
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+// f(VEL, FRAME): velocities or not; output frame 0 TEME, 1 ECEF, 2 geodetic (the kernels with a bool FRAME take FRAME != 0 and
+// choose ECEF / geodetic by p.mode)
+template <class F>
+void with_vel_frame(bool vel, int mode, F &&f)
+{
+    const int frame = mode == AZ_OUT_GEODETIC ? 2 : (mode != AZ_OUT_TEME ? 1 : 0);
+    with_bool(vel, [&](auto VEL) {
+        if (frame == 2) f(VEL, int_c<2>{});
+        else if (frame == 1) f(VEL, int_c<1>{});
+        else f(VEL, int_c<0>{});
+    });
+}
+// f(VEL, FRAME, SINK) of a lane = time launch: the fused screen's sink (TEME, no velocities, nothing stored) or the outputs in
+// fp64 / fp32
+template <class F>
+void with_outputs(const PropArgs &a, bool vel, F &&f)
+{
+    if (a.screen_target) return f(std::false_type{}, int_c<0>{}, int_c<AZ_SINK_SCREEN>{});
+    with_vel_frame(vel, a.mode, [&](auto VEL, auto FRAME) {
+        if (a.f32) f(VEL, FRAME, int_c<AZ_SINK_F32>{});
+        else f(VEL, FRAME, int_c<AZ_SINK_F64>{});
+    });
+}
+// grid deviations of a quasi-uniform grid: 0 none (exact grid), 1 tight (fp32 deviations), 2 wide (fp64)
+template <class F>
+void with_delta(int form, F &&f)
+{
+    if (form == 2) f(int_c<2>{});
+    else if (form == 1) f(int_c<1>{});
+    else f(int_c<0>{});
+}
+
+// `to` waits for everything enqueued on `from` so far: the fork of a side stream, and its join
+int32_t stream_after(hipStream_t to, hipStream_t from, hipEvent_t ev)
+{
+    HIP_TRY(hipEventRecord(ev, from));
+    HIP_TRY(hipStreamWaitEvent(to, ev, 0));
+    return AZ_OK;
 }
 
 // k_rows time segments: enough waves for ~4 rounds of 4 waves/SIMD, segments of >= 256 grid points,
@@ -562,9 +600,9 @@ unsigned screen_parts(const PropArgs &a, bool deep)
     if (use_rows(a, AZ_LAYOUT_SAT_MAJOR, deep)) {
         unsigned tile = rows_tile(a.n_list, a.n_times, a.tile_forced);
         if (deep) tile = std::min(tile, 64u * (unsigned)AZ_DEEP_SEED_MAX); // as launch_propagate
-        return (a.n_times + tile - 1) / tile;
+        return cgrid_y(a.n_times, tile);
     }
-    return (a.n_times + a.tile - 1) / a.tile;
+    return cgrid_y(a.n_times, a.tile);
 }
 
 // second stream for the eccentric-member launch of the row kernels (runs beside the near-circular bulk)
@@ -573,7 +611,6 @@ struct EccSide {
     hipEvent_t fork = nullptr, join = nullptr;
 };
 
-inline unsigned cgrid_y(unsigned n_times, unsigned tile) { return (n_times + tile - 1) / tile; }
 // launch shape of the fast kernels on a uniform grid: time-segment lengths of the near-circular and the eccentric launch,
 // which kernel family (= which window plan: 0 rows, 1 packed fp32 rows, 2 time-major tiles)
 struct FastShape {
@@ -623,123 +660,88 @@ FastShape fast_shape_tiles(const PropArgs &a, unsigned n_rows)
     return f;
 }
 
-// the fast kernels, exactly uniform or quasi-uniform grid (DELTA instantiations: fast_step.h)
+// k_rows_fast over n_slots list slots: exactly uniform or quasi-uniform grid (DELTA instantiations: fast_step.h); ECC: the
+// eccentric members' Kepler-Newton form
 template <bool VEL, int FRAME, int SINK, bool ECC>
-void launch_rows_fast(const PropArgs &a, dim3 grid, hipStream_t st)
+void launch_rows_fast(const PropArgs &a, unsigned n_slots, hipStream_t st)
 {
-    if (a.delta_wide) hipLaunchKernelGGL((k_rows_fast<VEL, FRAME, SINK, ECC, 2>), grid, dim3(64), 0, st, a);
-    else if (a.delta) hipLaunchKernelGGL((k_rows_fast<VEL, FRAME, SINK, ECC, 1>), grid, dim3(64), 0, st, a);
-    else hipLaunchKernelGGL((k_rows_fast<VEL, FRAME, SINK, ECC, 0>), grid, dim3(64), 0, st, a);
+    with_delta(a.delta_wide ? 2 : (a.delta ? 1 : 0), [&](auto DELTA) {
+        hipLaunchKernelGGL((k_rows_fast<VEL, FRAME, SINK, ECC, DELTA>), dim3(pad8(n_slots), cgrid_y(a.n_times, a.tile)), dim3(64), 0, st, a);
+    });
 }
-template <bool VEL, bool MIXED>
-void launch_rows_fast32(const PropArgs &a, dim3 grid, hipStream_t st)
+// the eccentric members of a [class 0 | other classes] list, segments of `tile` points.  Redo items carry (list slot, first,
+// end): their slots are offset into the common list
+PropArgs ecc_part(const PropArgs &a, unsigned tile)
 {
-    if (a.delta) hipLaunchKernelGGL((k_rows_fast32<VEL, MIXED, true>), grid, dim3(64), 0, st, a);
-    else hipLaunchKernelGGL((k_rows_fast32<VEL, MIXED, false>), grid, dim3(64), 0, st, a);
+    PropArgs e = a;
+    e.list = a.list + a.n_circ;
+    e.n_list = a.n_list - a.n_circ;
+    e.tile = tile;
+    e.redo_slot0 = a.n_circ;
+    return e;
 }
-template <bool VEL, int FRAME>
-void launch_tiles_fast(const PropArgs &a, dim3 grid, hipStream_t st)
+// the generic kernel over the redo list of a fast launch: the windows the plan's validation bounds rejected (static, known
+// before any kernel runs: well under one per cent of the segments) plus whatever the eccentric form's Newton validation handed
+// over.  Every workgroup takes items b, b + grid.x, ... and a quarter (grid.y = 4) of each
+template <bool VEL, int FRAME, int SINK>
+void launch_redo(const PropArgs &a, dim3 grid, hipStream_t st)
 {
-    // (both quasi-uniform forms run the WIDE instantiation here: it is a superset of the tight form's corrections, and in this
-    // kernel -- at its register limit -- the tight instantiation comes out with 28 B of scratch against 12 and measures 8 %
-    // slower, 0.318-0.322 against 0.296-0.299 ms same run)
-    if (a.delta64) hipLaunchKernelGGL((k_tiles_fast<VEL, FRAME, 2>), grid, dim3(1024), 0, st, a);
-    else hipLaunchKernelGGL((k_tiles_fast<VEL, FRAME, 0>), grid, dim3(1024), 0, st, a);
+    hipLaunchKernelGGL((k_rows<VEL, FRAME != 0, SINK, true>), grid, dim3(64), 0, st, a);
 }
 
-template <bool VEL, int FRAME> // FRAME: 0 TEME, 1 ECEF, 2 geodetic (the generic kernels take frame / no frame and p.mode)
-void launch_rows2(const PropArgs &a, dim3 grid, bool deep, hipStream_t st, const EccSide &side = EccSide(), const FastShape *shape = nullptr)
+// Near-earth rows on a uniform grid (a propagation's, and the fused screen's): the near-circular bulk runs alone on the launch
+// stream; beside it, on the side stream, the eccentric members (few rows) and then the redo pass over `rgrid`.  Nothing follows
+// the bulk launch on its stream: round 2's redo pass (12 us + two launch gaps per step) waited for it.
+int32_t launch_near_fast(const PropArgs &a, bool vel, const FastShape &shape, dim3 rgrid, hipStream_t st, const EccSide &side)
 {
-    constexpr bool FR = FRAME != 0;
-    if (deep) {
-        if (a.f32) hipLaunchKernelGGL((k_rows_deep<VEL, FR, AZ_SINK_F32>), grid, dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((k_rows_deep<VEL, FR, AZ_SINK_F64>), grid, dim3(64), 0, st, a);
-    } else if (a.redo_items != nullptr && shape != nullptr) {
-        // uniform grid: the branch-free kernels.  The near-circular bulk runs alone on the launch stream; beside it, on the
-        // side stream, the eccentric members (few rows) and then the generic kernel over the redo list -- the windows the
-        // plan's validation bounds rejected (static, known before any kernel runs: well under one per cent of the segments)
-        // plus whatever the eccentric form's Newton validation handed over.  Nothing follows the bulk launch on its stream:
-        // round 2's redo pass (12 us + two launch gaps per step) waited for it.
-        PropArgs e = a, c = a;
-        e.list = a.list + a.n_circ;
-        e.n_list = a.n_list - a.n_circ;
-        c.n_list = a.n_circ;
-        e.tile = shape->tile_e;
-        c.tile = shape->tile_c;
-        const bool packed32 = shape->packed32 && !FR;
-        // a row window: both launches are cut to the list slots it covers (their lists are in catalog order)
-        const bool win = a.row_lo > 0 || a.row_hi < a.n_rows;
-        unsigned n_e = e.n_list, n_c = c.n_list;
-        if (win) {
-            c.slot_lo = a.win_circ_lo; c.slot_hi = a.win_circ_hi; n_c = c.slot_hi - c.slot_lo;
-            e.slot_lo = a.win_ecc_lo; e.slot_hi = a.win_ecc_hi; n_e = e.slot_hi - e.slot_lo;
-            if (c.slot_hi == 0) c.n_list = n_c = 0; // (slot_hi = 0 means "whole list" to the kernels: an empty window launches nothing)
-            if (e.slot_hi == 0) e.n_list = n_e = 0;
-        }
-        dim3 egrid((n_e + 7) / 8 * 8, (a.n_times + e.tile - 1) / e.tile);
-        dim3 cgrid((n_c + 7) / 8 * 8, (a.n_times + c.tile - 1) / c.tile);
-        // the generic pass: every workgroup takes items b, b + gridDim.x, ... and a quarter of each; enough workgroups that a
-        // large catalog's rejected windows (1 % of 125,000 x 14 segments in config 5's share) do not queue up behind 1,024 waves
-        dim3 rgrid(std::min(8192u, std::max(256u, (a.n_list * cgrid_y(a.n_times, shape->tile_c) + 63u) / 64u)), 4);
-        // redo items carry (list slot, first, end): slots of the eccentric launch are offset into the common list
-        e.redo_slot0 = a.n_circ;
-        const bool beside = side.stream != nullptr && n_c;
-        hipStream_t se = beside ? side.stream : st;
-        if (beside) {
-            (void)hipEventRecord(side.fork, st);
-            (void)hipStreamWaitEvent(se, side.fork, 0);
-        }
-        if (n_e) {
-            if (a.f32) launch_rows_fast<VEL, FRAME, AZ_SINK_F32, true>(e, egrid, se);
-            else launch_rows_fast<VEL, FRAME, AZ_SINK_F64, true>(e, egrid, se);
-        }
-        if (a.f32) hipLaunchKernelGGL((k_rows<VEL, FR, AZ_SINK_F32, true>), rgrid, dim3(64), 0, se, a);
-        else hipLaunchKernelGGL((k_rows<VEL, FR, AZ_SINK_F64, true>), rgrid, dim3(64), 0, se, a);
-        if (n_c) {
-            if (packed32 && shape->mixed32) launch_rows_fast32<VEL, true>(c, cgrid, st);
-            else if (packed32) launch_rows_fast32<VEL, false>(c, cgrid, st);
-            else if (a.f32) launch_rows_fast<VEL, FRAME, AZ_SINK_F32, false>(c, cgrid, st);
-            else launch_rows_fast<VEL, FRAME, AZ_SINK_F64, false>(c, cgrid, st);
-        }
-        if (beside) {
-            (void)hipEventRecord(side.join, se);
-            (void)hipStreamWaitEvent(st, side.join, 0);
-        }
-    } else {
-        if (a.f32) hipLaunchKernelGGL((k_rows<VEL, FR, AZ_SINK_F32>), grid, dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((k_rows<VEL, FR, AZ_SINK_F64>), grid, dim3(64), 0, st, a);
+    PropArgs e = ecc_part(a, shape.tile_e), c = a;
+    c.n_list = a.n_circ;
+    c.tile = shape.tile_c;
+    // a row window: both launches are cut to the list slots it covers (their lists are in catalog order)
+    unsigned n_e = e.n_list, n_c = c.n_list;
+    if (a.row_lo > 0 || a.row_hi < a.n_rows) {
+        c.slot_lo = a.win_circ_lo; c.slot_hi = a.win_circ_hi; n_c = c.slot_hi - c.slot_lo;
+        e.slot_lo = a.win_ecc_lo; e.slot_hi = a.win_ecc_hi; n_e = e.slot_hi - e.slot_lo;
+        if (c.slot_hi == 0) c.n_list = n_c = 0; // (slot_hi = 0 means "whole list" to the kernels: an empty window launches nothing)
+        if (e.slot_hi == 0) e.n_list = n_e = 0;
     }
+    const bool beside = side.stream != nullptr && n_c;
+    const hipStream_t se = beside ? side.stream : st;
+    if (beside)
+        if (int32_t rc = stream_after(se, st, side.fork); rc != AZ_OK) return rc;
+    with_outputs(a, vel, [&](auto VEL, auto FRAME, auto SINK) {
+        if (n_e) launch_rows_fast<VEL, FRAME, SINK, true>(e, n_e, se);
+        launch_redo<VEL, FRAME, SINK>(a, rgrid, se);
+        if (n_c && FRAME == 0 && shape.packed32) // (fp32 TEME outputs: a lane of k_rows_fast32 carries two grid points)
+            with_bool(shape.mixed32, [&](auto MIXED) {
+                with_bool(a.delta != nullptr, [&](auto DELTA) {
+                    hipLaunchKernelGGL((k_rows_fast32<VEL, MIXED, DELTA>), dim3(pad8(n_c), cgrid_y(a.n_times, c.tile)), dim3(64), 0, st, c);
+                });
+            });
+        else if (n_c)
+            launch_rows_fast<VEL, FRAME, SINK, false>(c, n_c, st);
+    });
+    return beside ? stream_after(st, se, side.join) : AZ_OK;
 }
 
 // time-major output of the near-earth members on a uniform grid: 16-satellite tiles of lane = time waves (k_tiles_fast),
 // then the generic kernel on whatever their validation rejected (24-byte pieces, row by row)
 void launch_tiles(const PropArgs &a0, bool vel, hipStream_t st, const FastShape &shape)
 {
-    PropArgs a = a0;
-    a.tile = shape.tile_c;
-    const bool ecef = a.mode != AZ_OUT_TEME, geo = a.mode == AZ_OUT_GEODETIC;
-    dim3 grid(((a.n_rows + 15u) / 16u + 7u) / 8u * 8u, (a.n_times + a.tile - 1) / a.tile); // tiles of 16 catalog rows
-    if (geo) {
-        if (vel) launch_tiles_fast<true, 2>(a, grid, st);
-        else launch_tiles_fast<false, 2>(a, grid, st);
-    } else if (ecef) {
-        if (vel) launch_tiles_fast<true, 1>(a, grid, st);
-        else launch_tiles_fast<false, 1>(a, grid, st);
-    } else {
-        if (vel) launch_tiles_fast<true, 0>(a, grid, st);
-        else launch_tiles_fast<false, 0>(a, grid, st);
-    }
-    a.tm_rows = 1;
-    dim3 rgrid(256, 4);
-    if (ecef) {
-        if (vel) hipLaunchKernelGGL((k_rows<true, true, AZ_SINK_F64, true>), rgrid, dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((k_rows<false, true, AZ_SINK_F64, true>), rgrid, dim3(64), 0, st, a);
-    } else {
-        if (vel) hipLaunchKernelGGL((k_rows<true, false, AZ_SINK_F64, true>), rgrid, dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((k_rows<false, false, AZ_SINK_F64, true>), rgrid, dim3(64), 0, st, a);
-    }
+    PropArgs a = a0, r = a0;
+    a.tile = r.tile = shape.tile_c;
+    r.tm_rows = 1;
+    const dim3 grid(pad8((a.n_rows + 15u) / 16u), cgrid_y(a.n_times, a.tile)); // tiles of 16 catalog rows
+    with_vel_frame(vel, a.mode, [&](auto VEL, auto FRAME) {
+        // (both quasi-uniform forms run the WIDE instantiation here: it is a superset of the tight form's corrections, and in
+        // this kernel -- at its register limit -- the tight instantiation comes out with 28 B of scratch against 12 and measures
+        // 8 % slower, 0.318-0.322 against 0.296-0.299 ms same run)
+        with_bool(a.delta64 != nullptr, [&](auto WIDE) {
+            hipLaunchKernelGGL((k_tiles_fast<VEL, FRAME, WIDE ? 2 : 0>), grid, dim3(1024), 0, st, a);
+        });
+        launch_redo<VEL, FRAME, AZ_SINK_F64>(r, dim3(256, 4), st);
+    });
 }
-
 // time-major output through k_cols_fast (lane = satellite): segment length of the main launch.  A wave is 64 catalog rows x one
 // segment and runs for tens of microseconds, so a second, partly filled generation of waves would cost a large part of the
 // step: when one generation of AZ_COLS_WAVES waves per SIMD can hold the whole grid (config 2: 211 row groups x 19 segments of 76
@@ -764,102 +766,68 @@ FastShape fast_shape_cols(const PropArgs &a, unsigned n_rows, unsigned n_sgp4, u
     f.kind = 3;
     return f;
 }
-template <bool VEL, int FRAME>
-void launch_cols_fast(const PropArgs &a, dim3 grid, hipStream_t st)
-{
-    if (a.delta64) hipLaunchKernelGGL((k_cols_fast<VEL, FRAME, 2>), grid, dim3(64), 0, st, a);
-    else hipLaunchKernelGGL((k_cols_fast<VEL, FRAME, 0>), grid, dim3(64), 0, st, a);
-}
 // a: list = [class 0 | other classes], rowmap = the matching row map, tmp_pos / tmp_vel = the scratch array (deep-space rows
 // already in flight on their stream; the caller has made `st` wait for them)
-void launch_cols(const PropArgs &a0, bool vel, hipStream_t st, const FastShape &shape, const EccSide &side, unsigned ecc_row0)
+int32_t launch_cols(const PropArgs &a0, bool vel, hipStream_t st, const FastShape &shape, const EccSide &side, unsigned ecc_row0)
 {
     PropArgs a = a0;
-    const int frame = a.mode == AZ_OUT_GEODETIC ? 2 : (a.mode != AZ_OUT_TEME ? 1 : 0);
     // eccentric members: their own lane = time launch into the scratch array, beside whatever precedes the main launch
-    PropArgs e = a;
-    e.list = a.list + a.n_circ;
-    e.n_list = a.n_list - a.n_circ;
-    e.redo_slot0 = a.n_circ;
-    e.tile = shape.tile_e;
+    PropArgs e = ecc_part(a, shape.tile_e);
     e.pos = const_cast<double *>(a.tmp_pos);
     e.vel = vel ? const_cast<double *>(a.tmp_vel) : nullptr;
     e.rows_compact = 1;
     e.ecc_row0 = ecc_row0;
     if (e.n_list) {
-        dim3 egrid((e.n_list + 7) / 8 * 8, (a.n_times + e.tile - 1) / e.tile);
-        hipStream_t se = side.stream ? side.stream : st;
-        if (se != st) {
-            (void)hipEventRecord(side.fork, st);
-            (void)hipStreamWaitEvent(se, side.fork, 0);
-        }
-        if (frame == 2) { if (vel) launch_rows_fast<true, 2, AZ_SINK_F64, true>(e, egrid, se); else launch_rows_fast<false, 2, AZ_SINK_F64, true>(e, egrid, se); }
-        else if (frame == 1) { if (vel) launch_rows_fast<true, 1, AZ_SINK_F64, true>(e, egrid, se); else launch_rows_fast<false, 1, AZ_SINK_F64, true>(e, egrid, se); }
-        else { if (vel) launch_rows_fast<true, 0, AZ_SINK_F64, true>(e, egrid, se); else launch_rows_fast<false, 0, AZ_SINK_F64, true>(e, egrid, se); }
-        if (se != st) {
-            (void)hipEventRecord(side.join, se);
-            (void)hipStreamWaitEvent(st, side.join, 0);
-        }
+        const hipStream_t se = side.stream ? side.stream : st;
+        if (se != st)
+            if (int32_t rc = stream_after(se, st, side.fork); rc != AZ_OK) return rc;
+        with_vel_frame(vel, a.mode, [&](auto VEL, auto FRAME) { launch_rows_fast<VEL, FRAME, AZ_SINK_F64, true>(e, e.n_list, se); });
+        if (se != st)
+            if (int32_t rc = stream_after(st, se, side.join); rc != AZ_OK) return rc;
     }
     a.tile = shape.tile_c;
     a.ecc_row0 = ecc_row0;
-    dim3 grid(((a.n_rows + 63u) / 64u + 7u) / 8u * 8u, (a.n_times + a.tile - 1) / a.tile);
-    if (frame == 2) { if (vel) launch_cols_fast<true, 2>(a, grid, st); else launch_cols_fast<false, 2>(a, grid, st); }
-    else if (frame == 1) { if (vel) launch_cols_fast<true, 1>(a, grid, st); else launch_cols_fast<false, 1>(a, grid, st); }
-    else { if (vel) launch_cols_fast<true, 0>(a, grid, st); else launch_cols_fast<false, 0>(a, grid, st); }
-    // the generic pass over the windows the plan rejected and the eccentric form's hand-overs: 24-byte pieces, row by row
-    a.tm_rows = 1;
-    dim3 rgrid(256, 4);
-    if (frame) {
-        if (vel) hipLaunchKernelGGL((k_rows<true, true, AZ_SINK_F64, true>), rgrid, dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((k_rows<false, true, AZ_SINK_F64, true>), rgrid, dim3(64), 0, st, a);
-    } else {
-        if (vel) hipLaunchKernelGGL((k_rows<true, false, AZ_SINK_F64, true>), rgrid, dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((k_rows<false, false, AZ_SINK_F64, true>), rgrid, dim3(64), 0, st, a);
-    }
+    PropArgs r = a;
+    r.tm_rows = 1;
+    const dim3 grid(pad8((a.n_rows + 63u) / 64u), cgrid_y(a.n_times, a.tile));
+    with_vel_frame(vel, a.mode, [&](auto VEL, auto FRAME) {
+        with_bool(a.delta64 != nullptr, [&](auto WIDE) {
+            hipLaunchKernelGGL((k_cols_fast<VEL, FRAME, WIDE ? 2 : 0>), grid, dim3(64), 0, st, a);
+        });
+        // the generic pass over the windows the plan rejected and the eccentric form's hand-overs: 24-byte pieces, row by row
+        launch_redo<VEL, FRAME, AZ_SINK_F64>(r, dim3(256, 4), st);
+    });
+    return AZ_OK;
 }
 
-// returns the AZH_PATH_* bit of the kernel family it launched
-unsigned launch_propagate(const PropArgs &a, int layout, bool vel, bool deep, hipStream_t st, const EccSide &side = EccSide(),
-                          const FastShape *shape = nullptr)
+// the generic kernels, any grid (the uniform-grid kernels: launch_near_fast, launch_tiles, launch_cols); returns the
+// AZH_PATH_* bit of the kernel family it launched
+unsigned launch_propagate(const PropArgs &a, int layout, bool vel, bool deep, hipStream_t st)
 {
-    const bool frame = a.mode != AZ_OUT_TEME;
     if (use_rows(a, layout, deep)) {
         PropArgs b = a;
         b.tile = rows_tile(a.n_list, a.n_times, a.tile_forced);
         if (deep) b.tile = std::min(b.tile, 64u * (unsigned)AZ_DEEP_SEED_MAX); // k_rows_deep stages a segment's chunk seeds in LDS
         const unsigned n_slots = a.slot_hi ? a.slot_hi - a.slot_lo : a.n_list; // (a row window's share of a catalog-ordered list)
-        dim3 grid((n_slots + 7) / 8 * 8, (a.n_times + b.tile - 1) / b.tile);
-        if (deep || a.screen_target || a.inc == nullptr) b.redo_items = nullptr; // k_rows_fast: near-earth rows on a uniform grid
-        if (a.screen_target) {
-            if (deep) hipLaunchKernelGGL((k_rows_deep<false, false, AZ_SINK_SCREEN>), grid, dim3(64), 0, st, b);
-            else hipLaunchKernelGGL((k_rows<false, false, AZ_SINK_SCREEN>), grid, dim3(64), 0, st, b);
-        } else if (a.mode == AZ_OUT_GEODETIC) {
-            if (vel) launch_rows2<true, 2>(b, grid, deep, st, side, shape);
-            else launch_rows2<false, 2>(b, grid, deep, st, side, shape);
-        } else if (frame) {
-            if (vel) launch_rows2<true, 1>(b, grid, deep, st, side, shape);
-            else launch_rows2<false, 1>(b, grid, deep, st, side, shape);
-        } else {
-            if (vel) launch_rows2<true, 0>(b, grid, deep, st, side, shape);
-            else launch_rows2<false, 0>(b, grid, deep, st, side, shape);
-        }
-        return deep ? AZH_PATH_DEEP_ROWS : (!a.screen_target && b.redo_items != nullptr && shape != nullptr ? AZH_PATH_ROWS_FAST : AZH_PATH_ROWS_GENERIC);
+        const dim3 grid(pad8(n_slots), cgrid_y(a.n_times, b.tile));
+        with_outputs(a, vel, [&](auto VEL, auto FRAME, auto SINK) {
+            if (deep) hipLaunchKernelGGL((k_rows_deep<VEL, FRAME != 0, SINK>), grid, dim3(64), 0, st, b);
+            else hipLaunchKernelGGL((k_rows<VEL, FRAME != 0, SINK>), grid, dim3(64), 0, st, b);
+        });
+        return deep ? AZH_PATH_DEEP_ROWS : AZH_PATH_ROWS_GENERIC;
     }
-    if (a.screen_target) {
-        // fused screen, lane = satellite (deep-space members; near-earth on very short grids)
-        dim3 grid(((a.n_list + AZ_BLOCK - 1) / AZ_BLOCK + 7) / 8 * 8, (a.n_times + a.tile - 1) / a.tile);
-        if (deep) hipLaunchKernelGGL((k_propagate<0, false, true, false, true>), grid, dim3(AZ_BLOCK), 0, st, a);
-        else hipLaunchKernelGGL((k_propagate<0, false, false, false, true>), grid, dim3(AZ_BLOCK), 0, st, a);
-        return AZH_PATH_LANE_SAT;
-    }
-    if (deep) {
-        if (frame) launch_propagate2<true, true>(a, layout, vel, st);
-        else launch_propagate2<true, false>(a, layout, vel, st);
-    } else {
-        if (frame) launch_propagate2<false, true>(a, layout, vel, st);
-        else launch_propagate2<false, false>(a, layout, vel, st);
-    }
+    // lane = satellite; the fused screen (deep-space members, near-earth on very short grids) has its own instantiation
+    const dim3 grid(pad8((a.n_list + AZ_BLOCK - 1) / AZ_BLOCK), cgrid_y(a.n_times, a.tile));
+    with_bool(deep, [&](auto DEEP) {
+        if (a.screen_target)
+            hipLaunchKernelGGL((k_propagate<0, false, DEEP, false, true>), grid, dim3(AZ_BLOCK), 0, st, a);
+        else
+            with_bool(layout == AZ_LAYOUT_TIME_MAJOR, [&](auto TIME_MAJOR) {
+                with_vel_frame(vel, a.mode, [&](auto VEL, auto FRAME) {
+                    hipLaunchKernelGGL((k_propagate<TIME_MAJOR, VEL, DEEP, FRAME != 0>), grid, dim3(AZ_BLOCK), 0, st, a);
+                });
+            });
+    });
     return AZH_PATH_LANE_SAT;
 }
 
@@ -1189,8 +1157,7 @@ int32_t launch_all(azh_constellation *c, double *d_pos, double *d_vel, int layou
         if (int32_t rc = ensure_scratch(st); rc != AZ_OK) return rc;
     if (fork) {
         // deep-space rows on their own stream, concurrent with the near-earth launch
-        HIP_TRY(hipEventRecord(c->ev_fork, st));
-        HIP_TRY(hipStreamWaitEvent(c->s_deep, c->ev_fork, 0));
+        if (int32_t rc = stream_after(c->s_deep, st, c->ev_fork); rc != AZ_OK) return rc;
         PropArgs d = a;
         const bool deep_rows = use_rows(d, layout, true);
         const bool deep_skip = windowed && deep_rows && deep_hi == deep_lo; // (no deep-space row inside the window)
@@ -1219,6 +1186,8 @@ int32_t launch_all(azh_constellation *c, double *d_pos, double *d_vel, int layou
             path |= launch_propagate(d, layout, d_vel != nullptr, true, c->s_deep);
         }
         HIP_TRY(hipGetLastError());
+        // the join: recorded right behind the deep-space launches (s_deep may be the shared stream of small handles); the launch
+        // stream waits for it before the tile kernel, which copies the deep-space rows, or else at the end
         HIP_TRY(hipEventRecord(c->ev_join, c->s_deep));
     }
     if (c->n_sgp4 > 0) {
@@ -1246,14 +1215,21 @@ int32_t launch_all(azh_constellation *c, double *d_pos, double *d_vel, int layou
                          : (tiles ? fast_shape_tiles(a, (unsigned)c->n) : fast_shape_rows(a, c->n_sgp4, c->n_circ));
             if (int32_t rc = ensure_plan(c, a, shape, st); rc != AZ_OK) return rc;
         }
+        const EccSide side{c->s_ecc, c->ev_fork2, c->ev_join2};
         if (a.n_list > 0 && cols) {
-            launch_cols(a, d_vel != nullptr, st, shape, EccSide{c->s_ecc, c->ev_fork2, c->ev_join2}, c->n_sdp4);
+            if (int32_t rc = launch_cols(a, d_vel != nullptr, st, shape, side, c->n_sdp4); rc != AZ_OK) return rc;
             path |= AZH_PATH_COLS_FAST;
         } else if (a.n_list > 0 && tiles) {
             launch_tiles(a, d_vel != nullptr, st, shape);
             path |= AZH_PATH_TILES_FAST;
+        } else if (a.n_list > 0 && fast) {
+            // the redo pass: enough workgroups that a large catalog's rejected windows (1 % of 125,000 x 14 segments in config 5's
+            // share) do not queue up behind 1,024 waves
+            const dim3 rgrid(std::min(8192u, std::max(256u, (a.n_list * cgrid_y(a.n_times, shape.tile_c) + 63u) / 64u)), 4);
+            if (int32_t rc = launch_near_fast(a, d_vel != nullptr, shape, rgrid, st, side); rc != AZ_OK) return rc;
+            path |= AZH_PATH_ROWS_FAST;
         } else if (a.n_list > 0) {
-            path |= launch_propagate(a, layout, d_vel != nullptr, false, st, EccSide{c->s_ecc, c->ev_fork2, c->ev_join2}, fast ? &shape : nullptr);
+            path |= launch_propagate(a, layout, d_vel != nullptr, false, st);
         }
         if ((a.delta || a.delta64) && (path & (AZH_PATH_TILES_FAST | AZH_PATH_ROWS_FAST | AZH_PATH_COLS_FAST))) path |= AZH_PATH_QUASI_UNIFORM;
         HIP_TRY(hipGetLastError());
@@ -2203,26 +2179,8 @@ static int32_t screen_core(azh_constellation *c, const double *times, size_t n_t
         }
         if (c->n_sgp4 > 0) {
             if (fast_screen) {
-                PropArgs e = near, cc = near;
-                e.list = near.list + near.n_circ;
-                e.n_list = near.n_list - near.n_circ;
-                e.tile = shape.tile_e;
-                e.redo_slot0 = near.n_circ;
-                cc.n_list = near.n_circ;
                 // as in a propagation: the bulk alone on the launch stream, the eccentric members and the generic pass beside it
-                const bool beside = cc.n_list > 0;
-                hipStream_t se = beside ? c->s_ecc : st;
-                if (beside) {
-                    HIP_TRY(hipEventRecord(c->ev_fork2, st));
-                    HIP_TRY(hipStreamWaitEvent(se, c->ev_fork2, 0));
-                }
-                if (e.n_list) launch_rows_fast<false, 0, AZ_SINK_SCREEN, true>(e, dim3((e.n_list + 7) / 8 * 8, cgrid_y(nt, e.tile)), se);
-                hipLaunchKernelGGL((k_rows<false, false, AZ_SINK_SCREEN, true>), dim3(256, 4), dim3(64), 0, se, near);
-                if (cc.n_list) launch_rows_fast<false, 0, AZ_SINK_SCREEN, false>(cc, dim3((cc.n_list + 7) / 8 * 8, cgrid_y(nt, cc.tile)), st);
-                if (beside) {
-                    HIP_TRY(hipEventRecord(c->ev_join2, se));
-                    HIP_TRY(hipStreamWaitEvent(st, c->ev_join2, 0));
-                }
+                if ((rc = launch_near_fast(near, false, shape, dim3(256, 4), st, EccSide{c->s_ecc, c->ev_fork2, c->ev_join2})) != AZ_OK) return rc;
                 c->last_path = AZH_PATH_ROWS_FAST | ((near.delta || near.delta64) ? AZH_PATH_QUASI_UNIFORM : 0u);
             } else {
                 c->last_path = launch_propagate(near, AZ_LAYOUT_SAT_MAJOR, false, false, st);
