@@ -174,12 +174,14 @@ class Sgp4Constellation:
         return [float(x) for x in self._dev.epochs]
 
     def propagate_into(self, times, positions, velocities=None, *, epoch_offsets=None, satellite_mask=None,
-                       output="ecef", reference_jd=0.0, time_major=True, output_stride=-1):
+                       output="ecef", reference_jd=0.0, time_major=True, output_stride=-1, observer=None):
         """Propagate into caller-owned arrays (sgp4.zig L170-262): ``(n_times, stride, 3)`` if `time_major`
         else ``(n_sats, n_times, 3)``; ``output_stride`` > 0 overrides the row length of the time-major
-        layout; raises ValueError when an array is too small."""
-        if output not in _native.OUTPUT_MODES:
-            raise ValueError("output must be 'ecef', 'teme', or 'geodetic'")
+        layout; raises ValueError when an array is too small.  ``output="topocentric"`` needs
+        ``observer=(lat_deg, lon_deg, alt_km)`` (see :func:`propagate`)."""
+        _check_output(output, observer)
+        if observer is not None:
+            self._dev.set_observer(*_observer3(observer))
         mask = None if satellite_mask is None else np.ascontiguousarray(satellite_mask).astype(np.uint8)
         self._dev.propagate_host(times, epoch_offsets, pos=positions, vel=velocities,
                                  mode=_native.OUTPUT_MODES[output], reference_jd=float(reference_jd), mask=mask,
@@ -239,6 +241,28 @@ class Constellation:
         return self._catalog_index.copy()
 
 
+_OUTPUT_ERROR = "output must be 'ecef', 'teme', 'geodetic' or 'topocentric'"
+
+
+def _observer3(observer):
+    try:
+        lat, lon, alt = (float(x) for x in observer)
+    except (TypeError, ValueError):
+        raise ValueError("observer must be (lat_deg, lon_deg, alt_km)") from None
+    if not (np.isfinite([lat, lon, alt]).all() and abs(lat) <= 90.0):
+        raise ValueError("observer must be finite with |lat_deg| <= 90")
+    return lat, lon, alt
+
+
+def _check_output(output, observer):
+    if output not in _native.OUTPUT_MODES:
+        raise ValueError(_OUTPUT_ERROR)
+    if output == "topocentric" and observer is None:
+        raise ValueError("output='topocentric' needs observer=(lat_deg, lon_deg, alt_km)")
+    if output != "topocentric" and observer is not None:
+        raise ValueError("observer= applies to output='topocentric' only")
+
+
 def _minutes_and_offsets(const, times, start_time):
     minutes = np.ascontiguousarray(times, dtype=np.float64)
     start = _jd_of(start_time)
@@ -246,16 +270,21 @@ def _minutes_and_offsets(const, times, start_time):
 
 
 def propagate(source, times, *, start_time=None, output="ecef", velocities=False, norad_id=None, fetch=None,
-              allow_network=False):
+              allow_network=False, observer=None):
     """Propagate satellites to ``times`` (minutes from ``start_time``, default now).
 
     Returns positions ``(n_times, n_satellites, 3)`` [km; or (lat rad, lon rad, alt km) for
     ``output="geodetic"`` -- radians, as the reference's kernel emits (Constellation.zig L497)], plus
-    velocities ``(n_times, n_satellites, 3)`` km/s if ``velocities=True``.  Reference: __init__.py L411-532."""
+    velocities ``(n_times, n_satellites, 3)`` km/s if ``velocities=True``.  Reference: __init__.py L411-532.
+
+    ``output="topocentric"`` with ``observer=(lat_deg, lon_deg, alt_km)`` (geodetic WGS84): look angles from the observer,
+    (azimuth rad from north toward east in [0, 2 pi), elevation rad, range km), and with ``velocities=True`` their rates
+    (rad/s, rad/s, km/s) -- the range rate is that of the Earth-fixed relative velocity (Doppler)."""
     const = source if isinstance(source, Constellation) else Constellation(source, norad_id=norad_id, fetch=fetch,
                                                                            allow_network=allow_network)
-    if output not in _native.OUTPUT_MODES:
-        raise ValueError("output must be 'ecef', 'teme', or 'geodetic'")
+    _check_output(output, observer)
+    if observer is not None:
+        const._dev.set_observer(*_observer3(observer))
     minutes, offsets, start = _minutes_and_offsets(const, times, start_time)
     shape = (len(minutes), const.num_satellites, 3)
     pos = _native.result_empty(shape)     # (large results: pinned memory the device-to-host DMA writes directly)
@@ -263,6 +292,42 @@ def propagate(source, times, *, start_time=None, output="ecef", velocities=False
     const._dev.propagate_host(minutes, offsets, pos=pos, vel=vel, mode=_native.OUTPUT_MODES[output],
                               reference_jd=start, layout=_native.TIME_MAJOR)
     return (pos, vel) if velocities else pos
+
+
+def passes(source, times, observer, *, min_elevation=10.0, start_time=None, norad_id=None, fetch=None, allow_network=False):
+    """Passes of every satellite over a ground station during ``times`` (minutes from ``start_time``, default now; strictly
+    increasing).  ``observer=(lat_deg, lon_deg, alt_km)`` geodetic WGS84; ``min_elevation`` in degrees.
+
+    Returns a numpy structured array, one row per pass, sorted by (sat, rise): ``sat`` (output row), ``rise``,
+    ``culmination``, ``set`` (minutes from ``start_time``, refined between grid points by cubic Hermite interpolation of the
+    elevation and its rate), ``max_elevation``, ``rise_azimuth``, ``set_azimuth`` (rad) and ``flags`` (1: already up at the
+    first time, 2: still up at the last, 4: cut by a failed propagation; an open end is the grid time).  The propagation and
+    the search run on the GPU; only the pass records come back."""
+    lat, lon, alt = _observer3(observer)
+    const = source if isinstance(source, Constellation) else Constellation(source, norad_id=norad_id, fetch=fetch,
+                                                                           allow_network=allow_network)
+    minutes, offsets, start = _minutes_and_offsets(const, times, start_time)
+    if len(minutes) > 1 and not (np.diff(minutes) > 0).all():
+        raise ValueError("times must be strictly increasing")
+    const._dev.set_observer(lat, lon, alt)
+    rec, cnt = const._dev.find_passes(minutes, offsets, reference_jd=start, min_elevation_deg=float(min_elevation), max_passes=16)
+    if cnt.size and int(cnt.max()) > rec.shape[1]:  # more passes than room: once more with room for all of them
+        rec, cnt = const._dev.find_passes(minutes, offsets, reference_jd=start, min_elevation_deg=float(min_elevation),
+                                          max_passes=int(cnt.max()))
+    sat = np.repeat(np.arange(len(cnt), dtype=np.uint32), cnt)
+    k = np.concatenate([np.arange(c, dtype=np.intp) for c in cnt]) if len(cnt) else np.zeros(0, dtype=np.intp)
+    r = rec[sat, k] if len(sat) else rec.reshape(-1)[:0]
+    out = np.empty(len(sat), dtype=PASS_DTYPE)
+    out["sat"] = sat
+    out["rise"], out["culmination"], out["set"] = r["t_rise_min"], r["t_culm_min"], r["t_set_min"]
+    out["max_elevation"], out["rise_azimuth"], out["set_azimuth"] = r["max_elevation_rad"], r["rise_azimuth_rad"], r["set_azimuth_rad"]
+    out["flags"] = r["flags"]
+    return out
+
+
+# passes(): one row per pass
+PASS_DTYPE = np.dtype([("sat", "<u4"), ("rise", "<f8"), ("culmination", "<f8"), ("set", "<f8"), ("max_elevation", "<f8"),
+                       ("rise_azimuth", "<f8"), ("set_azimuth", "<f8"), ("flags", "<u4")])
 
 
 def screen(source, times, threshold=10.0, *, target=None, start_time=None, norad_id=None, fetch=None, allow_network=False):
@@ -341,7 +406,7 @@ def escape_velocity(mu, radius):
     return _scalar(_native.lib().orbital_escape_velocity(float(mu), float(radius)), "orbital_escape_velocity", "invalid radius")
 
 
-__all__ = ["__version__", "Tle", "Sgp4Constellation", "Constellation", "propagate", "screen", "coarse_screen",
+__all__ = ["__version__", "Tle", "Sgp4Constellation", "Constellation", "propagate", "passes", "screen", "coarse_screen",
            "set_fetcher", "celestrak_url", "WGS72", "WGS84", "hohmann_transfer", "orbital_velocity", "orbital_period",
            "escape_velocity", "EARTH_MU", "EARTH_R_EQ", "EARTH_J2", "SUN_MU", "MOON_MU"]
 # (the reference's package also re-exports bi_elliptic_transfer, lambert and propagate_numerical -- its orbital-mechanics and

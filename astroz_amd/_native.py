@@ -13,9 +13,14 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ASTROZ_AMD_LIB") or os.path.join(_HERE, "libastroz_hip.so")
 
 WGS84, WGS72 = 0, 1
-OUT_TEME, OUT_ECEF, OUT_GEODETIC = 0, 1, 2
+OUT_TEME, OUT_ECEF, OUT_GEODETIC, OUT_TOPOCENTRIC = 0, 1, 2, 3
 SAT_MAJOR, TIME_MAJOR = 0, 1
-OUTPUT_MODES = {"teme": OUT_TEME, "ecef": OUT_ECEF, "geodetic": OUT_GEODETIC}
+OUTPUT_MODES = {"teme": OUT_TEME, "ecef": OUT_ECEF, "geodetic": OUT_GEODETIC, "topocentric": OUT_TOPOCENTRIC}
+# azh_pass (include/astroz_hip.h) and its flags
+PASS_DTYPE = np.dtype([("t_rise_min", "<f8"), ("t_culm_min", "<f8"), ("t_set_min", "<f8"), ("max_elevation_rad", "<f8"),
+                       ("rise_azimuth_rad", "<f8"), ("set_azimuth_rad", "<f8"), ("flags", "<u4"), ("grid_rise", "<u4"),
+                       ("grid_culm", "<u4"), ("grid_set", "<u4")])
+PASS_UP_AT_START, PASS_UP_AT_END, PASS_CUT_BY_ERROR = 1, 2, 4
 
 AZ_ERR_HIP = -200
 # azh_last_path bits (include/astroz_hip.h)
@@ -40,6 +45,7 @@ EXPORTS = [
     "azh_group_propagate_allgather", "azh_group_screen_target_host", "azh_group_screen_target_device", "azh_group_shard_size",
     "azh_group_shard_rows", "azh_group_synchronize", "azh_screen_track_device", "coords_eci_to_ecef", "coords_ecef_to_geodetic",
     "orbital_hohmann", "orbital_velocity", "orbital_period", "orbital_escape_velocity",
+    "azh_coords_topocentric", "azh_set_observer", "azh_find_passes_host", "azh_find_passes_device",
 ]
 
 
@@ -237,6 +243,14 @@ def lib():
     L.azh_coarse_screen_host.restype = i32
     L.azh_screen_all_host.argtypes = [vp, vp, sz, vp, dbl, vp, vp, sz, C.POINTER(sz)]
     L.azh_screen_all_host.restype = i32
+    L.azh_coords_topocentric.argtypes = [vp, vp, dbl, vp, vp, vp]
+    L.azh_coords_topocentric.restype = None
+    L.azh_set_observer.argtypes = [vp, dbl, dbl, dbl]
+    L.azh_set_observer.restype = i32
+    L.azh_find_passes_host.argtypes = [vp, vp, sz, vp, dbl, dbl, vp, sz, vp]
+    L.azh_find_passes_host.restype = i32
+    L.azh_find_passes_device.argtypes = [vp, vp, sz, vp, dbl, dbl, vp, sz, vp, vp]
+    L.azh_find_passes_device.restype = i32
     L.orbital_hohmann.argtypes = [dbl, dbl, dbl, vp]
     L.orbital_hohmann.restype = i32
     for f, n in (("orbital_velocity", 3), ("orbital_period", 2), ("orbital_escape_velocity", 2)):
@@ -436,6 +450,35 @@ class DeviceConstellation:
         ex = C.c_size_t(-1).value if exclude is None else int(exclude)
         check(lib().azh_screen_track_device(self._h, times.ctypes.data, len(times), _ptr(off), d_track, ex, float(threshold),
                                             d_min_dist, d_min_t, stream), "azh_screen_track_device")
+
+    # -- ground station: look angles and passes ----------------------------------------------------
+    def set_observer(self, lat_deg, lon_deg, alt_km=0.0):
+        """Observer of OUT_TOPOCENTRIC and of the pass finder: geodetic WGS84 (degrees, degrees, km)."""
+        check(lib().azh_set_observer(self._h, float(lat_deg), float(lon_deg), float(alt_km)), "azh_set_observer")
+
+    def find_passes(self, times_min, offsets_min=None, *, reference_jd=0.0, min_elevation_deg=10.0, max_passes=16):
+        """Passes above min_elevation_deg seen from the observer (azh_find_passes_host): (records (n, max_passes) of
+        PASS_DTYPE, n_passes (n,) u32 -- the TRUE count per satellite, which may exceed max_passes)."""
+        times = _f64(times_min)
+        off = None if offsets_min is None else _f64(offsets_min)
+        if off is not None and len(off) < self.n:
+            raise ValueError("epoch_offsets must have at least num_satellites elements")
+        out = np.zeros((self.n, int(max_passes)), dtype=PASS_DTYPE)
+        cnt = np.zeros(self.n, dtype=np.uint32)
+        check(lib().azh_find_passes_host(self._h, times.ctypes.data, len(times), _ptr(off), float(reference_jd),
+                                         float(min_elevation_deg), out.ctypes.data if max_passes else None, int(max_passes),
+                                         cnt.ctypes.data), "azh_find_passes_host")
+        return out, cnt
+
+    def find_passes_device(self, times_min, offsets_min, d_out, max_passes, d_n_passes, *, reference_jd=0.0,
+                           min_elevation_deg=10.0, stream=None):
+        """azh_find_passes_device: d_out / d_n_passes are raw device pointers (n x max_passes records of PASS_DTYPE, n u32);
+        asynchronous."""
+        times = _f64(times_min)
+        off = None if offsets_min is None else _f64(offsets_min)
+        check(lib().azh_find_passes_device(self._h, times.ctypes.data, len(times), _ptr(off), float(reference_jd),
+                                           float(min_elevation_deg), d_out, int(max_passes), d_n_passes, stream),
+              "azh_find_passes_device")
 
     def screen_all(self, times_min, threshold=10.0, offsets_min=None, max_results=10_000_000):
         """All-vs-all: propagate on the device and screen there: (pairs (k,2) u32, t_index (k,) u32),

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "passes_kernel.h"
 #include "tle_host.h"
 #include "host_step.h"
 
@@ -247,6 +248,13 @@ struct azh_constellation {
     DevBuf<double> d_host_pos, d_host_vel; // azh_propagate_host: grow-only device-side result buffers
     DevBuf<unsigned char> d_host_err;
     bool have_offsets = false, have_mask = false;
+    AzObserver obs{};          // AZ_OUT_TOPOCENTRIC and the pass finder (azh_set_observer) ...
+    DevBuf<AzObserver> d_obs;  // ... and its device copy, refreshed by the first launch after a change (obs_dirty)
+    bool have_observer = false, obs_dirty = false;
+    DevBuf<double> d_pass_pos, d_pass_vel; // azh_find_passes_*: grow-only topocentric scratch of one row window
+    DevBuf<unsigned char> d_pass_err;
+    DevBuf<azh_pass> d_pass_out;          // ... and the records / counts of azh_find_passes_host
+    DevBuf<uint32_t> d_pass_n;
     unsigned cached_n_times = 0;
     int cached_mode = 0;
     unsigned off_cat = 0; // d_list + off_cat: near-earth members in plain catalog order (k_tiles_fast: runs of consecutive rows)
@@ -534,18 +542,21 @@ void with_bool(bool b, F &&f)
     if (b) f(std::true_type{});
     else f(std::false_type{});
 }
-// f(VEL, FRAME): velocities or not; output frame 0 TEME, 1 ECEF, 2 geodetic (the kernels with a bool FRAME take FRAME != 0 and
-// choose ECEF / geodetic by p.mode)
+// f(VEL, FRAME): velocities or not; output frame 0 TEME, 1 ECEF, 2 geodetic, 3 topocentric (the generic kernels take
+// gen_frame(FRAME): they choose ECEF / geodetic by p.mode at run time)
 template <class F>
 void with_vel_frame(bool vel, int mode, F &&f)
 {
-    const int frame = mode == AZ_OUT_GEODETIC ? 2 : (mode != AZ_OUT_TEME ? 1 : 0);
+    const int frame = mode == AZ_OUT_TOPOCENTRIC ? 3 : (mode == AZ_OUT_GEODETIC ? 2 : (mode != AZ_OUT_TEME ? 1 : 0));
     with_bool(vel, [&](auto VEL) {
-        if (frame == 2) f(VEL, int_c<2>{});
+        if (frame == 3) f(VEL, int_c<3>{});
+        else if (frame == 2) f(VEL, int_c<2>{});
         else if (frame == 1) f(VEL, int_c<1>{});
         else f(VEL, int_c<0>{});
     });
 }
+// the generic kernels' FRAME (k_propagate, k_rows, k_rows_deep): 0 TEME, 1 ECEF / geodetic by p.mode, 3 topocentric
+constexpr int gen_frame(int frame) { return frame == 3 ? 3 : (frame != 0 ? 1 : 0); }
 // f(VEL, FRAME, SINK) of a lane = time launch: the fused screen's sink (TEME, no velocities, nothing stored) or the outputs in
 // fp64 / fp32
 template <class F>
@@ -686,7 +697,7 @@ PropArgs ecc_part(const PropArgs &a, unsigned tile)
 template <bool VEL, int FRAME, int SINK>
 void launch_redo(const PropArgs &a, dim3 grid, hipStream_t st)
 {
-    hipLaunchKernelGGL((k_rows<VEL, FRAME != 0, SINK, true>), grid, dim3(64), 0, st, a);
+    hipLaunchKernelGGL((k_rows<VEL, gen_frame(FRAME), SINK, true>), grid, dim3(64), 0, st, a);
 }
 
 // Near-earth rows on a uniform grid (a propagation's, and the fused screen's): the near-circular bulk runs alone on the launch
@@ -811,8 +822,8 @@ unsigned launch_propagate(const PropArgs &a, int layout, bool vel, bool deep, hi
         const unsigned n_slots = a.slot_hi ? a.slot_hi - a.slot_lo : a.n_list; // (a row window's share of a catalog-ordered list)
         const dim3 grid(pad8(n_slots), cgrid_y(a.n_times, b.tile));
         with_outputs(a, vel, [&](auto VEL, auto FRAME, auto SINK) {
-            if (deep) hipLaunchKernelGGL((k_rows_deep<VEL, FRAME != 0, SINK>), grid, dim3(64), 0, st, b);
-            else hipLaunchKernelGGL((k_rows<VEL, FRAME != 0, SINK>), grid, dim3(64), 0, st, b);
+            if (deep) hipLaunchKernelGGL((k_rows_deep<VEL, gen_frame(FRAME), SINK>), grid, dim3(64), 0, st, b);
+            else hipLaunchKernelGGL((k_rows<VEL, gen_frame(FRAME), SINK>), grid, dim3(64), 0, st, b);
         });
         return deep ? AZH_PATH_DEEP_ROWS : AZH_PATH_ROWS_GENERIC;
     }
@@ -820,11 +831,11 @@ unsigned launch_propagate(const PropArgs &a, int layout, bool vel, bool deep, hi
     const dim3 grid(pad8((a.n_list + AZ_BLOCK - 1) / AZ_BLOCK), cgrid_y(a.n_times, a.tile));
     with_bool(deep, [&](auto DEEP) {
         if (a.screen_target)
-            hipLaunchKernelGGL((k_propagate<0, false, DEEP, false, true>), grid, dim3(AZ_BLOCK), 0, st, a);
+            hipLaunchKernelGGL((k_propagate<0, false, DEEP, 0, true>), grid, dim3(AZ_BLOCK), 0, st, a);
         else
             with_bool(layout == AZ_LAYOUT_TIME_MAJOR, [&](auto TIME_MAJOR) {
                 with_vel_frame(vel, a.mode, [&](auto VEL, auto FRAME) {
-                    hipLaunchKernelGGL((k_propagate<TIME_MAJOR, VEL, DEEP, FRAME != 0>), grid, dim3(AZ_BLOCK), 0, st, a);
+                    hipLaunchKernelGGL((k_propagate<TIME_MAJOR, VEL, DEEP, gen_frame(FRAME)>), grid, dim3(AZ_BLOCK), 0, st, a);
                 });
             });
     });
@@ -1098,6 +1109,16 @@ int32_t launch_all(azh_constellation *c, double *d_pos, double *d_vel, int layou
     a.err = d_err;
     a.stride_sats = stride;
     a.mode = c->cached_mode;
+    if (a.mode == AZ_OUT_TOPOCENTRIC) {
+        // the observer record on the device: uploaded on the launch stream ahead of the first launch after azh_set_observer
+        if (c->obs_dirty) {
+            if (c->capturing) return AZ_RC_EAGER;
+            if (c->d_obs.ensure(1) != AZ_OK) return AZ_ERR_HIP;
+            HIP_TRY(hipMemcpyAsync(c->d_obs.p, &c->obs, sizeof(AzObserver), hipMemcpyHostToDevice, st)); // (pageable: read on return)
+            c->obs_dirty = false;
+        }
+        a.obs = c->d_obs.p;
+    }
     a.f32 = f32;
     a.arith32 = f32 ? c->f32_mode : 2;
     a.g = c->g;
@@ -2030,7 +2051,8 @@ static int32_t propagate_device(azh_constellation *c, const double *times, size_
 {
     return guarded([&]() -> int32_t {
         if (!c || !d_pos || (n_times && !times)) return AZ_ERR_NULL_POINTER;
-        if (mode < 0 || mode > 2 || layout < 0 || layout > 1) return AZ_ERR_VALUE;
+        if (mode < 0 || mode > AZ_OUT_TOPOCENTRIC || layout < 0 || layout > 1) return AZ_ERR_VALUE;
+        if (mode == AZ_OUT_TOPOCENTRIC && !c->have_observer) return AZ_ERR_VALUE;
         if (n_times == 0) return AZ_OK; // an empty grid is valid and produces nothing
         if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
         hipStream_t st = stream ? (hipStream_t)stream : c->s_main;
@@ -2435,6 +2457,152 @@ int32_t azh_screen_all_host(azh_constellation *c, const double *times, size_t n_
             rc = coarse_screen(d_pos, c->n, n_times, AZ_LAYOUT_TIME_MAJOR, 0, threshold_km, nullptr, out_pairs, out_t,
                                max_results, n_found, c->s_main, 1);
         (void)hipStreamSynchronize(c->s_main);
+        return rc;
+    });
+}
+
+// ---- topocentric look angles and ground-station passes ----------------------------------------------------------------
+namespace {
+// geodetic WGS84 (deg, deg, km) -> the kernels' observer record (the ellipsoid of az_ecef_to_geodetic)
+bool observer_ok(double lat_deg, double lon_deg, double alt_km)
+{
+    return std::isfinite(lat_deg) && std::isfinite(lon_deg) && std::isfinite(alt_km) && std::fabs(lat_deg) <= 90.0;
+}
+AzObserver make_observer(double lat_deg, double lon_deg, double alt_km)
+{
+    const double f = 1.0 / 298.257223563, e2 = 2.0 * f - f * f, a = 6378.137;
+    const double lat = lat_deg * (AZ_PI / 180.0), lon = lon_deg * (AZ_PI / 180.0);
+    AzObserver o;
+    o.sin_lat = std::sin(lat); o.cos_lat = std::cos(lat);
+    o.sin_lon = std::sin(lon); o.cos_lon = std::cos(lon);
+    const double N = a / std::sqrt(1.0 - e2 * o.sin_lat * o.sin_lat);
+    o.x = (N + alt_km) * o.cos_lat * o.cos_lon;
+    o.y = (N + alt_km) * o.cos_lat * o.sin_lon;
+    o.z = (N * (1.0 - e2) + alt_km) * o.sin_lat;
+    return o;
+}
+} // namespace
+
+void azh_coords_topocentric(const double r_teme[3], const double v_teme[3], double gmst, const double observer_lla[3], double aer[3],
+                            double aer_rate[3])
+{
+    if (!r_teme || !observer_lla || !aer) return;
+    // the device epilogue's arithmetic (az_topocentric, propagate_device.h) with libm's atan2 / sqrt
+    const AzObserver o = make_observer(observer_lla[0], observer_lla[1], observer_lla[2]);
+    const double sg = std::sin(gmst), cg = std::cos(gmst);
+    const double rx = r_teme[0] * cg + r_teme[1] * sg, ry = r_teme[1] * cg - r_teme[0] * sg, rz = r_teme[2];
+    const double dx = rx - o.x, dy = ry - o.y, dz = rz - o.z;
+    const double q = o.cos_lon * dx + o.sin_lon * dy;
+    const double E = o.cos_lon * dy - o.sin_lon * dx, N = o.cos_lat * dz - o.sin_lat * q, U = o.cos_lat * q + o.sin_lat * dz;
+    const double h2 = E * E + N * N, r2 = U * U + h2, h = std::sqrt(h2), rng = std::sqrt(r2);
+    const bool overhead = h < 1.0e-9;
+    double az = std::atan2(E, N);
+    if (az < 0.0) az += 2.0 * AZ_PI;
+    if (overhead || az >= 2.0 * AZ_PI) az = 0.0;
+    aer[0] = az;
+    aer[1] = std::atan2(U, h);
+    aer[2] = rng;
+    if (!aer_rate) return;
+    aer_rate[0] = aer_rate[1] = aer_rate[2] = 0.0;
+    if (!v_teme) return;
+    const double w = AZ_OMEGA_EARTH;
+    const double vx = v_teme[0] * cg + v_teme[1] * sg + w * ry, vy = v_teme[1] * cg - v_teme[0] * sg - w * rx, vz = v_teme[2];
+    const double qd = o.cos_lon * vx + o.sin_lon * vy;
+    const double Ed = o.cos_lon * vy - o.sin_lon * vx, Nd = o.cos_lat * vz - o.sin_lat * qd, Ud = o.cos_lat * qd + o.sin_lat * vz;
+    const double hhd = E * Ed + N * Nd;
+    aer_rate[0] = overhead ? 0.0 : (Ed * N - E * Nd) / h2;
+    aer_rate[1] = overhead ? 0.0 : (h2 * Ud - U * hhd) / (h * r2);
+    aer_rate[2] = rng > 0.0 ? (U * Ud + hhd) / rng : 0.0;
+}
+
+int32_t azh_set_observer(azh_constellation *c, double lat_deg, double lon_deg, double alt_km)
+{
+    return guarded([&]() -> int32_t {
+        if (!c) return AZ_ERR_NULL_POINTER;
+        if (!observer_ok(lat_deg, lon_deg, alt_km)) return AZ_ERR_VALUE;
+        if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
+        drop_graphs(c); // (a captured launch set holds the old observer in its kernel arguments)
+        c->obs = make_observer(lat_deg, lon_deg, alt_km);
+        c->have_observer = true;
+        c->obs_dirty = true;
+        return AZ_OK;
+    });
+}
+
+// azh_find_passes_*: propagate to AZ_OUT_TOPOCENTRIC with rates, satellite-major, into the handle's scratch one row window at a
+// time (at most kPassScratch bytes: pos + vel + err), and scan every window's rows with k_passes behind its propagation
+static constexpr size_t kPassScratch = size_t(512) << 20;
+static int32_t find_passes(azh_constellation *c, const double *times, size_t n_times, const double *offsets, double reference_jd,
+                           double min_elevation_deg, azh_pass *d_out, size_t max_passes, uint32_t *d_n, hipStream_t st)
+{
+    if (!c->have_observer || !std::isfinite(min_elevation_deg) || max_passes > 0xffffffffu) return AZ_ERR_VALUE;
+    for (size_t i = 1; i < n_times; ++i)
+        if (!(times[i] > times[i - 1])) return AZ_ERR_VALUE; // (the Hermite interval needs a length > 0; NaN fails too)
+    if (c->n == 0) return AZ_OK;
+    if (n_times == 0) {
+        HIP_TRY(hipMemsetAsync(d_n, 0, sizeof(uint32_t) * c->n, st));
+        return AZ_OK;
+    }
+    if (int32_t rc = stage_inputs(c, times, n_times, offsets, nullptr, AZ_OUT_TOPOCENTRIC, reference_jd, st); rc != AZ_OK) return rc;
+    const size_t per_row = n_times * (6 * sizeof(double) + 1);
+    const size_t rows_w = std::max<size_t>(1, std::min(c->n, kPassScratch / per_row));
+    const size_t words = rows_w * n_times * 3;
+    if (c->d_pass_pos.cap < words || c->d_pass_vel.cap < words || c->d_pass_err.cap < rows_w * n_times)
+        HIP_TRY(hipStreamSynchronize(st)); // (launches in flight use the old buffers)
+    if (c->d_pass_pos.ensure(words) != AZ_OK || c->d_pass_vel.ensure(words) != AZ_OK || c->d_pass_err.ensure(rows_w * n_times) != AZ_OK)
+        return AZ_ERR_HIP;
+    for (size_t lo = 0; lo < c->n; lo += rows_w) {
+        const size_t hi = std::min(c->n, lo + rows_w);
+        // the window's rows land at the start of the scratch: the launch writes rows [lo, hi) of arrays based lo rows earlier
+        const size_t shift = lo * n_times;
+        const uintptr_t pb = reinterpret_cast<uintptr_t>(c->d_pass_pos.p) - 3 * shift * sizeof(double);
+        const uintptr_t vb = reinterpret_cast<uintptr_t>(c->d_pass_vel.p) - 3 * shift * sizeof(double);
+        const uintptr_t eb = reinterpret_cast<uintptr_t>(c->d_pass_err.p) - shift;
+        if (int32_t rc = launch_all(c, reinterpret_cast<double *>(pb), reinterpret_cast<double *>(vb), AZ_LAYOUT_SAT_MAJOR, 0,
+                                    reinterpret_cast<uint8_t *>(eb), st, 0, lo, hi);
+            rc != AZ_OK)
+            return rc;
+        PassArgs q{};
+        q.pos = c->d_pass_pos.p; q.vel = c->d_pass_vel.p; q.err = c->d_pass_err.p;
+        q.times = c->d_times.p; q.n_times = (unsigned)n_times;
+        q.row0 = (unsigned)lo; q.n_rows = (unsigned)(hi - lo);
+        q.min_el = min_elevation_deg * (AZ_PI / 180.0);
+        q.out = d_out; q.max_passes = (unsigned)max_passes; q.n_passes = d_n;
+        hipLaunchKernelGGL(k_passes, dim3((unsigned)((hi - lo + AZ_PASS_WAVES - 1) / AZ_PASS_WAVES)), dim3(64 * AZ_PASS_WAVES), 0, st, q);
+        HIP_TRY(hipGetLastError());
+    }
+    return AZ_OK;
+}
+
+int32_t azh_find_passes_device(azh_constellation *c, const double *times, size_t n_times, const double *offsets, double reference_jd,
+                               double min_elevation_deg, azh_pass *d_out, size_t max_passes, uint32_t *d_n_passes, void *stream)
+{
+    return guarded([&]() -> int32_t {
+        if (!c || !d_n_passes || (n_times && !times) || (max_passes && !d_out)) return AZ_ERR_NULL_POINTER;
+        if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
+        return find_passes(c, times, n_times, offsets, reference_jd, min_elevation_deg, d_out, max_passes, d_n_passes,
+                           stream ? (hipStream_t)stream : c->s_main);
+    });
+}
+
+int32_t azh_find_passes_host(azh_constellation *c, const double *times, size_t n_times, const double *offsets, double reference_jd,
+                             double min_elevation_deg, azh_pass *out, size_t max_passes, uint32_t *n_passes)
+{
+    return guarded([&]() -> int32_t {
+        if (!c || !n_passes || (n_times && !times) || (max_passes && !out)) return AZ_ERR_NULL_POINTER;
+        if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
+        if (c->n == 0) return find_passes(c, times, n_times, offsets, reference_jd, min_elevation_deg, nullptr, max_passes, nullptr, c->s_main);
+        const size_t n_rec = c->n * max_passes;
+        if (c->d_pass_out.cap < n_rec || c->d_pass_n.cap < c->n) HIP_TRY(hipStreamSynchronize(c->s_main));
+        if ((n_rec && c->d_pass_out.ensure(n_rec) != AZ_OK) || c->d_pass_n.ensure(c->n) != AZ_OK) return AZ_ERR_HIP;
+        int32_t rc = find_passes(c, times, n_times, offsets, reference_jd, min_elevation_deg, n_rec ? c->d_pass_out.p : nullptr, max_passes,
+                                 c->d_pass_n.p, c->s_main);
+        if (rc == AZ_OK && !hip_ok(hipMemcpyAsync(n_passes, c->d_pass_n.p, sizeof(uint32_t) * c->n, hipMemcpyDeviceToHost, c->s_main), "D2H"))
+            rc = AZ_ERR_HIP;
+        if (rc == AZ_OK && n_rec &&
+            !hip_ok(hipMemcpyAsync(out, c->d_pass_out.p, sizeof(azh_pass) * n_rec, hipMemcpyDeviceToHost, c->s_main), "D2H"))
+            rc = AZ_ERR_HIP;
+        if (!hip_ok(hipStreamSynchronize(c->s_main), "sync") && rc == AZ_OK) rc = AZ_ERR_HIP;
         return rc;
     });
 }

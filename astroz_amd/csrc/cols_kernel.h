@@ -68,10 +68,11 @@ __device__ __forceinline__ double az_sload(const double *q)
 }
 
 // grid: x = groups of 64 catalog rows (padded to a multiple of 8: XCD-aware, az_xcd_row), y = time segments of p.tile points
-template <bool VEL, int FRAME, int DELTA> // FRAME: 0 TEME, 1 ECEF, 2 geodetic positions (+ ECEF velocities); DELTA: 0 exact grid, 2 quasi-uniform (fp64 deviations)
-__global__ void __launch_bounds__(64, (FRAME == 2 && VEL) ? 2 : AZ_COLS_WAVES) k_cols_fast(PropArgs p) // (geodetic + velocities: 2 waves/SIMD, no spill)
+template <bool VEL, int FRAME, int DELTA> // FRAME: 0 TEME, 1 ECEF, 2 geodetic positions (+ ECEF velocities), 3 topocentric; DELTA: 0 exact grid, 2 quasi-uniform (fp64 deviations)
+__global__ void __launch_bounds__(64, (FRAME >= 2 && VEL) ? 2 : AZ_COLS_WAVES) k_cols_fast(PropArgs p) // (geodetic / topocentric + velocities: 2 waves/SIMD, no spill)
 {
     constexpr unsigned NA = VEL ? 2u : 1u;
+    [[maybe_unused]] const AzObserver obs = FRAME == 3 ? *p.obs : AzObserver{}; // (topocentric output: the observer record, read once)
     __shared__ __attribute__((aligned(16))) double col_lds[CL_NUM * 64];
     __shared__ __attribute__((aligned(16))) double stage[NA * AZ_TM_ROW];
     const unsigned lane = threadIdx.x;
@@ -163,6 +164,7 @@ __global__ void __launch_bounds__(64, (FRAME == 2 && VEL) ? 2 : AZ_COLS_WAVES) k
                 az_to_ecef(r, sg, cg);
                 if (VEL) az_to_ecef(v, sg, cg);
                 if (FRAME == 2) az_ecef_to_geodetic(r);
+                if (FRAME == 3) az_topocentric<VEL>(r, v, obs);
             }
             if (COPY) {
                 // this step's copied values, then -- into the same registers, ahead of this step's stores -- the next step's

@@ -77,7 +77,12 @@ struct PropArgs {
     // fused single-target conjunction screen (sink instead of stores): the target's TEME track,
     // [n_times][3], NaN where the target itself failed; partial minima per (segment or tile, list slot)
     const double *screen_target;
-    double *part_d2;
+    // ... which no launch with a topocentric epilogue has: FRAME 3 kernels find the observer record (device memory) in its place
+    // (a member appended to this struct would move every kernel's hidden-argument loads)
+    union {
+        double *part_d2;
+        const AzObserver *obs;
+    };
     unsigned *part_t;
     // uniform grids: times[i] = times[0] + i * uniform_step (0 = not uniform), and the per-satellite
     // rotation increments k_prep_inc prepared for it (fast_step.h); null = generic path only
@@ -176,6 +181,16 @@ __device__ __forceinline__ void az_epilogue(double r[3], double v[3], int mode, 
         if (mode == 2) az_ecef_to_geodetic(r);
     }
 }
+// the generic kernels' topocentric epilogue (FRAME 3): a compile-time choice, so that the run-time one above -- and the
+// instantiations that carry it -- stay as they are
+template <bool VEL>
+__device__ __forceinline__ void az_epilogue_topo(double r[3], double v[3], const PropArgs &p, unsigned i)
+{
+    const double sg = p.sin_g[i], cg = p.cos_g[i];
+    az_to_ecef(r, sg, cg);
+    if (VEL) az_to_ecef(v, sg, cg);
+    az_topocentric<VEL>(r, v, *p.obs);
+}
 
 // LDS staging.  All staging is wave-private (each wave owns a slice of the array and only ever
 // exchanges data between its own lanes), so no s_barrier and -- more importantly -- no
@@ -236,9 +251,9 @@ __device__ __forceinline__ void az_tm_flush(const double *L, double *row, size_t
     }
 }
 
-// FRAME = false: TEME output, no epilogue code at all (keeps its registers and SGPRs out of the
-// hot kernel); FRAME = true: ECEF / geodetic chosen at run time by p.mode.
-template <int LAYOUT, bool VEL, bool DEEP, bool FRAME, bool SCREEN = false>
+// FRAME = 0: TEME output, no epilogue code at all (keeps its registers and SGPRs out of the
+// hot kernel); FRAME = 1: ECEF / geodetic chosen at run time by p.mode; FRAME = 3: topocentric.
+template <int LAYOUT, bool VEL, bool DEEP, int FRAME, bool SCREEN = false>
 // (round 6: the time-major deep-space instantiations -- grids shorter than 32 points only, everything longer takes k_rows_deep --
 // get a whole SIMD's registers: at two waves they spilled 12-28 bytes for nothing)
 __global__ void __launch_bounds__(AZ_BLOCK, (AZ_MIN_WAVES > 1 ? AZ_MIN_WAVES : (FRAME ? 1 : (DEEP ? (LAYOUT == 1 ? 1 : AZ_DEEP_WAVES) : 3)))) k_propagate(PropArgs p)
@@ -287,7 +302,8 @@ __global__ void __launch_bounds__(AZ_BLOCK, (AZ_MIN_WAVES > 1 ? AZ_MIN_WAVES : (
 
     // what happens to one step's result: the fused screen, or the store path of the layout
     auto emit = [&](unsigned i, double (&r)[3], double (&v)[3], int rc) {
-        if (FRAME) az_epilogue(r, v, p.mode, VEL, p.sin_g, p.cos_g, i);
+        if (FRAME == 3) az_epilogue_topo<VEL>(r, v, p, i);
+        else if (FRAME) az_epilogue(r, v, p.mode, VEL, p.sin_g, p.cos_g, i);
         if (SCREEN) {
             // fused single-target screen (lane = satellite): running minimum over this tile, no stores
             const double *q = p.screen_target + (size_t)i * 3; // wave-uniform address
@@ -1036,7 +1052,7 @@ __global__ void __launch_bounds__(64, 3) k_one_fast(const double *el, const unsi
 // (near-circular Kepler form), ECC = true for the other classes (general form).  A window the plan rejected is already an
 // item of the redo list and its wave exits at once; a wave of the eccentric form whose Newton iteration needs more than
 // its five fixed-tier trips appends the rest of its segment to that list; the generic kernel runs the list beside the bulk.
-// FRAME: 0 TEME, 1 ECEF, 2 geodetic (compile-time: the geodetic conversion's registers stay out of the ECEF kernel).  The
+// FRAME: 0 TEME, 1 ECEF, 2 geodetic, 3 topocentric (compile-time: the geodetic conversion's registers stay out of the ECEF kernel).  The
 // (sin,cos) of the Greenwich angle of AZ_FRAME_SEG points of this wave's segment at a time (refilled inside the loop)
 // are staged in LDS before the loop: no table load inside it (round 2's FRAME kernels loaded two doubles per iteration,
 // each load waiting for the stores in flight, and carried the run-time choice of ECEF / geodetic: 149-173 VGPRs + scratch).
@@ -1047,11 +1063,12 @@ __global__ void __launch_bounds__(64, 3) k_one_fast(const double *el, const unsi
 // DELTA: quasi-uniform grid (fast_step.h): the segment's deviations delta_i, staged in LDS as fp32 before the loop (|delta| <=
 // 4e-6 min: an fp32 delta is good to 2.4e-13 min, the rounding of t itself), ride on the time value and on the small rotation of U.
 template <bool VEL, int FRAME, int SINK, bool ECC, int DELTA = 0> // DELTA: 0 exact grid, 1 tight (fp32 deviations), 2 wide (fp64)
-__global__ void __launch_bounds__(64, FRAME == 2 ? 4 : (ECC ? AZ_ROWSF_ECC_WAVES : (FRAME == 1 || DELTA == 2 ? 5 : AZ_ROWSF_WAVES))) k_rows_fast(PropArgs p)
+__global__ void __launch_bounds__(64, FRAME >= 2 ? 4 : (ECC ? AZ_ROWSF_ECC_WAVES : (FRAME == 1 || DELTA == 2 ? 5 : AZ_ROWSF_WAVES))) k_rows_fast(PropArgs p)
 {
     typedef typename std::conditional<SINK == AZ_SINK_F32, float, double>::type out_t;
     const unsigned lane = threadIdx.x;
     const unsigned row = az_list_slot(p); // XCD-aware row assignment, see k_rows
+    [[maybe_unused]] const AzObserver obs = FRAME == 3 ? *p.obs : AzObserver{}; // (topocentric output: the observer record, read once)
     if (row >= az_list_end(p)) return;
     const unsigned s = p.list[row]; // wave-uniform
     if (SINK != AZ_SINK_SCREEN && ((p.mask != nullptr && p.mask[s] == 0) || s < p.row_lo || s >= p.row_hi)) return;
@@ -1165,6 +1182,7 @@ __global__ void __launch_bounds__(64, FRAME == 2 ? 4 : (ECC ? AZ_ROWSF_ECC_WAVES
                 az_to_ecef(r, sg, cg);
                 if (VEL) az_to_ecef(v, sg, cg);
                 if (FRAME == 2) az_ecef_to_geodetic(r);
+                if (FRAME == 3) az_topocentric<VEL>(r, v, obs);
             }
 #if defined(AZ_ABLATE) && AZ_ABLATE == 1 /* tuning experiment: arithmetic only (every component stays live) */
             if (!(live && (r[0] + r[1] + r[2] + (VEL ? v[0] + v[1] + v[2] : 0.0)) == 1.2345e300)) continue;
@@ -1205,11 +1223,12 @@ __global__ void __launch_bounds__(64, FRAME == 2 ? 4 : (ECC ? AZ_ROWSF_ECC_WAVES
 #define AZ_TILE_SATS 16
 #define AZ_TILE_SEG_MAX 1024 /* longest time segment of an ECEF launch (its Greenwich-angle table sits in LDS) */
 #define AZ_TILE_PITCH 49 /* doubles per staged time row: 48 + 1 (lane stride 98 dwords: ds_write_b64 conflict-free per half-wave) */
-template <bool VEL, int FRAME = 0, int DELTA = 0> // FRAME: 0 TEME, 1 ECEF, 2 geodetic positions (+ ECEF velocities); DELTA: see k_rows_fast
+template <bool VEL, int FRAME = 0, int DELTA = 0> // FRAME: 0 TEME, 1 ECEF, 2 geodetic positions (+ ECEF velocities), 3 topocentric; DELTA: see k_rows_fast
 __global__ void __launch_bounds__(1024, 1) k_tiles_fast(PropArgs p)
 {
     constexpr unsigned NA = VEL ? 2u : 1u;
     constexpr bool ECEF = FRAME != 0;
+    [[maybe_unused]] const AzObserver obs = FRAME == 3 ? *p.obs : AzObserver{}; // (topocentric output: the observer record, read once)
     __shared__ __attribute__((aligned(16))) double cold_all[AZ_TILE_SATS * AZ_FAST_TABLE];
     __shared__ __attribute__((aligned(16))) double tile[2 * NA * 64 * AZ_TILE_PITCH];
     // ECEF output: (sin,cos) of the Greenwich angle of this segment's time steps, staged once (a load inside the loop would
@@ -1326,6 +1345,7 @@ __global__ void __launch_bounds__(1024, 1) k_tiles_fast(PropArgs p)
                 az_to_ecef(r, sg, cg);
                 if (VEL) az_to_ecef(v, sg, cg);
                 if (FRAME == 2) az_ecef_to_geodetic(r);
+                if (FRAME == 3) az_topocentric<VEL>(r, v, obs);
             }
             if (az_any(bad && live)) {
                 dead = true;
@@ -1548,7 +1568,7 @@ __global__ void __launch_bounds__(64, MIXED ? AZ_ROWSF32P_WAVES : AZ_ROWSF32_WAV
 //   REDO: grid (N, 4)                       -- the items k_rows_fast rejected; every workgroup takes items
 //                                               blockIdx.x, +gridDim.x, ... and a quarter (blockIdx.y) of each,
 //                                               so that the few items are spread over the whole chip.
-template <bool VEL, bool FRAME, int SINK, bool REDO = false>
+template <bool VEL, int FRAME, int SINK, bool REDO = false> // FRAME: as k_propagate's
 __global__ void __launch_bounds__(64, AZ_ROWS_WAVES) k_rows(PropArgs p)
 {
     typedef typename std::conditional<SINK == AZ_SINK_F32, float, double>::type out_t;
@@ -1652,7 +1672,8 @@ __global__ void __launch_bounds__(64, AZ_ROWS_WAVES) k_rows(PropArgs p)
             }
             continue;
         }
-        if (FRAME) az_epilogue(r, v, p.mode, VEL, p.sin_g, p.cos_g, live ? i : t_hi - 1);
+        if (FRAME == 3) az_epilogue_topo<VEL>(r, v, p, live ? i : t_hi - 1);
+        else if (FRAME) az_epilogue(r, v, p.mode, VEL, p.sin_g, p.cos_g, live ? i : t_hi - 1);
 #if defined(AZ_ABLATE) && AZ_ABLATE == 1 /* tuning experiment: arithmetic only (every component stays live) */
         if (!(live && (r[0] + r[1] + r[2] + (VEL ? v[0] + v[1] + v[2] : 0.0)) == 1.2345e300)) continue;
 #endif
@@ -1697,7 +1718,7 @@ __global__ void __launch_bounds__(64, AZ_ROWS_WAVES) k_rows(PropArgs p)
 #define AZ_ROWSD_WAVES 3
 #endif
 #define AZ_DEEP_SEED_MAX 64 /* chunk seeds of one time segment staged in LDS: segments of at most 64 x 64 grid points */
-template <bool VEL, bool FRAME, int SINK>
+template <bool VEL, int FRAME, int SINK> // FRAME: as k_propagate's
 __global__ void __launch_bounds__(64, AZ_ROWSD_WAVES) k_rows_deep(PropArgs p)
 {
     typedef typename std::conditional<SINK == AZ_SINK_F32, float, double>::type out_t;
@@ -1791,7 +1812,8 @@ __global__ void __launch_bounds__(64, AZ_ROWSD_WAVES) k_rows_deep(PropArgs p)
             }
             continue;
         }
-        if (FRAME) az_epilogue(r, v, p.mode, VEL, p.sin_g, p.cos_g, live ? i : t_hi - 1);
+        if (FRAME == 3) az_epilogue_topo<VEL>(r, v, p, live ? i : t_hi - 1);
+        else if (FRAME) az_epilogue(r, v, p.mode, VEL, p.sin_g, p.cos_g, live ? i : t_hi - 1);
         if (rc != 0) {
             r[0] = r[1] = r[2] = 0.0;
             v[0] = v[1] = v[2] = 0.0;

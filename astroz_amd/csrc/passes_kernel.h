@@ -1,0 +1,278 @@
+// passes_kernel.h -- ground-station pass search over a topocentric scratch array (azh_find_passes_*).  Included only by
+// astroz_hip.hip, after kernels.h.
+//
+// Input: one row window of AZ_OUT_TOPOCENTRIC output with rates, satellite-major -- per row and grid point (az, el, range),
+// (az rate, el rate, range rate) and the propagation error code.  One wave per row, lanes on 64 consecutive grid points: every
+// load is a coalesced run of the row.  A point is "up" when it propagated (err == 0) and el >= min_el; rises and sets are the
+// 0 -> 1 and 1 -> 0 transitions of a 64-bit ballot of that predicate, with the last lane's state carried from one iteration to
+// the next.  Events are rare (at most ~16 per LEO satellite and day against 1,440 grid points), so the lane that owns an event
+// refines it alone and the wave then walks the event bits in lane order, keeping the pass under way in wave-uniform registers;
+// the running maximum of a pass is a wave max over the lanes of its segment.
+//
+// Refinement (nothing is propagated again): on the bracketing interval [t0, t1] of a rise or set, elevation is the cubic
+// Hermite interpolant of (el, el rate x 60) at both ends -- per minute, over the true interval length -- and the event time is
+// its root inside the bracket: safeguarded Newton from the linear estimate, bisection whenever a step leaves the bracket.  The
+// azimuth there is interpolated the same way after unwrapping a1 to within pi of a0.  The culmination is the grid maximum of
+// the pass; on each of its two adjacent intervals where the elevation rate changes sign (+ to -) the highest point of the
+// Hermite-interpolated topocentric track (az_culmination) replaces it if it is higher.  Open ends (grid start / end, a failed
+// neighbour) keep the grid value.
+#pragma once
+#include "../../include/astroz_hip.h"
+
+struct PassArgs {
+    const double *pos, *vel;  // [row - row0][n_times][3]: (az, el, range), (az rate, el rate, range rate)
+    const unsigned char *err; // [row - row0][n_times]
+    const double *times;      // the caller's time axis (minutes), strictly increasing
+    unsigned n_times;
+    unsigned row0, n_rows; // catalog rows [row0, row0 + n_rows) of this window
+    double min_el;         // rad
+    azh_pass *out;         // [n_sats][max_passes]
+    unsigned max_passes;
+    uint32_t *n_passes; // [n_sats]
+};
+
+// cubic Hermite on s in [0, 1]: values f0, f1, end slopes m0, m1 (already scaled by the interval length)
+__device__ __forceinline__ double az_herm(double f0, double f1, double m0, double m1, double s)
+{
+    const double s2 = s * s, s3 = s2 * s;
+    return (2.0 * s3 - 3.0 * s2 + 1.0) * f0 + (s3 - 2.0 * s2 + s) * m0 + (3.0 * s2 - 2.0 * s3) * f1 + (s3 - s2) * m1;
+}
+__device__ __forceinline__ double az_herm_d(double f0, double f1, double m0, double m1, double s)
+{
+    return (6.0 * s * s - 6.0 * s) * (f0 - f1) + (3.0 * s * s - 4.0 * s + 1.0) * m0 + (3.0 * s * s - 2.0 * s) * m1;
+}
+// root in [0, 1] of the Hermite interpolant (f0 and f1 of opposite sign or zero): safeguarded Newton from the linear estimate
+__device__ __forceinline__ double az_herm_root(double f0, double f1, double m0, double m1)
+{
+    auto g = [&](double s) { return az_herm(f0, f1, m0, m1, s); };
+    auto dg = [&](double s) { return az_herm_d(f0, f1, m0, m1, s); };
+    const double g0 = f0, g1 = f1;
+    if (g0 == 0.0) return 0.0;
+    if (g1 == 0.0) return 1.0;
+    double lo = 0.0, hi = 1.0, s = g0 / (g0 - g1);
+    for (int it = 0; it < 64; ++it) {
+        const double gs = g(s);
+        if (gs == 0.0) break;
+        if ((gs < 0.0) == (g0 < 0.0)) lo = s;
+        else hi = s;
+        const double d = dg(s);
+        double sn = d != 0.0 ? s - gs / d : lo;
+        if (!(sn > lo && sn < hi)) sn = 0.5 * (lo + hi);
+        const bool done = fabs(sn - s) <= 1e-15;
+        s = sn;
+        if (done) break;
+    }
+    return s;
+}
+// azimuth on [0, 1]: a1 unwrapped to within pi of a0, Hermite, back into [0, 2 pi)
+__device__ __forceinline__ double az_herm_azimuth(double a0, double a1, double m0, double m1, double s)
+{
+    double d = a1 - a0;
+    d -= AZ_TWOPI * rint(d * (1.0 / AZ_TWOPI));
+    double a = az_herm(a0, a0 + d, m0, m1, s);
+    a -= AZ_TWOPI * floor(a * (1.0 / AZ_TWOPI));
+    return (a >= AZ_TWOPI || a < 0.0) ? 0.0 : a;
+}
+
+// culmination: the grid points' topocentric ENU positions and velocities (rebuilt from (az, el, range) and their rates) are
+// interpolated component by component with cubic Hermites, and the elevation of that track is maximised: the root of the
+// sign of its derivative, which the end rates fix, by regula falsi with the Illinois correction (about ten evaluations).
+// (Hermite on the elevation itself is good for rises and sets but not at the top of a high pass, whose time scale -- range /
+// speed, about a minute in LEO -- is the grid step: 1e-2 rad too low at 60 degrees on a one-minute grid, against 3e-7 rad
+// this way; measured on two-body passes.)
+__device__ __forceinline__ void az_enu_state(const double *P, const double *V, double c[3][2])
+{
+    double se, ce, sa, ca;
+    az_sincos(P[1], se, ce);
+    az_sincos(P[0], sa, ca);
+    const double h = P[2] * ce, hd = V[2] * ce - P[2] * se * V[1];
+    c[0][0] = h * sa; c[0][1] = hd * sa + h * ca * V[0];        // E, dE/dt
+    c[1][0] = h * ca; c[1][1] = hd * ca - h * sa * V[0];        // N
+    c[2][0] = P[2] * se; c[2][1] = V[2] * se + P[2] * ce * V[1]; // U
+}
+// elevation of the highest point of the track on [t0, t1] (dt minutes; the elevation rate is > 0 at t0 and < 0 at t1), and
+// its place s in [0, 1]
+__device__ __forceinline__ double az_culmination(const double *P0, const double *V0, const double *P1, const double *V1, double dt,
+                                                 double &s_out)
+{
+    double a[3][2], b[3][2];
+    az_enu_state(P0, V0, a);
+    az_enu_state(P1, V1, b);
+    const double k = 60.0 * dt;
+    double x[3], xd[3];
+    auto track = [&](double s) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            x[j] = az_herm(a[j][0], b[j][0], k * a[j][1], k * b[j][1], s);
+            xd[j] = az_herm_d(a[j][0], b[j][0], k * a[j][1], k * b[j][1], s);
+        }
+    };
+    auto slope = [&](double s) { // h^2 r^2 x (d elevation / ds)
+        track(s);
+        return (x[0] * x[0] + x[1] * x[1]) * xd[2] - x[2] * (x[0] * xd[0] + x[1] * xd[1]);
+    };
+    double lo = 0.0, hi = 1.0, g_lo = slope(0.0), g_hi = slope(1.0), s = 0.5;
+    int side = 0;
+    for (int it = 0; it < 40 && g_lo > 0.0 && g_hi < 0.0; ++it) {
+        const double sn = (lo * g_hi - hi * g_lo) / (g_hi - g_lo);
+        const bool done = fabs(sn - s) <= 1e-14;
+        s = sn;
+        const double gs = slope(s);
+        if (done || gs == 0.0) break;
+        if (gs > 0.0) {
+            lo = s; g_lo = gs;
+            if (side == 1) g_hi *= 0.5;
+            side = 1;
+        } else {
+            hi = s; g_hi = gs;
+            if (side == -1) g_lo *= 0.5;
+            side = -1;
+        }
+    }
+    s_out = s;
+    track(s);
+    const double h2 = x[0] * x[0] + x[1] * x[1];
+    return az_atan2(x[2], h2 * az_rsqrt(fmax(h2, 1.0e-300)));
+}
+
+__device__ __forceinline__ double az_wave_max(double x)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) x = fmax(x, __shfl_xor(x, o, 64));
+    return x;
+}
+
+#define AZ_PASS_WAVES 4
+__global__ void __launch_bounds__(64 * AZ_PASS_WAVES) k_passes(PassArgs p)
+{
+    const unsigned lane = threadIdx.x & 63u;
+    const unsigned wrow = blockIdx.x * AZ_PASS_WAVES + (threadIdx.x >> 6);
+    if (wrow >= p.n_rows) return; // (wave-uniform)
+    const unsigned n = p.n_times;
+    const double *P = p.pos + (size_t)wrow * n * 3, *V = p.vel + (size_t)wrow * n * 3;
+    const unsigned char *E = p.err + (size_t)wrow * n;
+    const double *T = p.times;
+    const size_t srow = (size_t)p.row0 + wrow;
+    azh_pass *out = p.out + srow * p.max_passes;
+    const double min_el = p.min_el;
+
+    // the pass under way (wave-uniform)
+    bool in_pass = false;
+    unsigned count = 0;
+    azh_pass cur{};
+    double best_el = -1.0e300;
+    unsigned best_i = 0;
+    uint64_t carry_up = 0, carry_bad = 0; // state of the grid point before this iteration's first
+
+    // the record of a pass whose set is known: culmination refinement, store (the first max_passes only)
+    auto finish = [&]() {
+        double t_c = T[best_i], e_c = best_el;
+        const unsigned k = best_i;
+#pragma unroll
+        for (int side = 0; side < 2; ++side) {
+            if (side == 0 && k == 0) continue;
+            if (side == 1 && k + 1 >= n) continue;
+            const unsigned i0 = side == 0 ? k - 1 : k, i1 = i0 + 1;
+            if (E[i0] != 0 || E[i1] != 0) continue;
+            const double d0 = V[3 * (size_t)i0 + 1], d1 = V[3 * (size_t)i1 + 1];
+            if (!(d0 > 0.0 && d1 < 0.0)) continue;
+            const double dt = T[i1] - T[i0];
+            double s;
+            const double e = az_culmination(P + 3 * (size_t)i0, V + 3 * (size_t)i0, P + 3 * (size_t)i1, V + 3 * (size_t)i1, dt, s);
+            if (e > e_c) {
+                e_c = e;
+                t_c = fma(s, dt, T[i0]);
+            }
+        }
+        cur.t_culm_min = t_c;
+        cur.max_elevation_rad = e_c;
+        cur.grid_culm = k;
+        if (lane == 0 && count < p.max_passes) out[count] = cur;
+        ++count;
+    };
+
+    for (unsigned base = 0; base < n; base += 64) {
+        const unsigned i = base + lane;
+        const bool live = i < n;
+        const double el = live ? P[3 * (size_t)i + 1] : 0.0;
+        const bool bad = live && E[i] != 0;
+        const bool up = live && !bad && el >= min_el;
+        const uint64_t m = __ballot(up), mb = __ballot(bad), ml = __ballot(live);
+        const uint64_t prev = (m << 1) | carry_up, prevb = (mb << 1) | carry_bad;
+        const uint64_t rises = m & ~prev, sets = ~m & prev & ml;
+        const bool is_rise = (rises >> lane) & 1u, is_set = (sets >> lane) & 1u;
+        // refinement by the lane that owns the event: time, azimuth and flag of a rise (interval [i-1, i], i first up point)
+        // or a set (interval [i-1, i], i-1 last up point)
+        double ev_t = 0.0, ev_az = 0.0;
+        unsigned ev_fl = 0;
+        if (is_rise || is_set) {
+            const bool prev_bad = (prevb >> lane) & 1u;
+            if (is_rise && i == 0) {
+                ev_t = T[0];
+                ev_az = P[0];
+                ev_fl = AZH_PASS_UP_AT_START;
+            } else if ((is_rise && prev_bad) || (is_set && bad)) {
+                const unsigned j = is_rise ? i : i - 1; // the open end stays on the grid point that propagated
+                ev_t = T[j];
+                ev_az = P[3 * (size_t)j];
+                ev_fl = AZH_PASS_CUT_BY_ERROR;
+            } else {
+                const unsigned i0 = i - 1;
+                const double dt = T[i] - T[i0];
+                const double f0 = P[3 * (size_t)i0 + 1] - min_el, f1 = el - min_el;
+                const double s = az_herm_root(f0, f1, 60.0 * dt * V[3 * (size_t)i0 + 1], 60.0 * dt * V[3 * (size_t)i + 1]);
+                ev_t = fma(s, dt, T[i0]);
+                ev_az = az_herm_azimuth(P[3 * (size_t)i0], P[3 * (size_t)i], 60.0 * dt * V[3 * (size_t)i0], 60.0 * dt * V[3 * (size_t)i], s);
+            }
+        }
+        // the segment [lo, hi) of this iteration belongs to the pass under way: its grid maximum (earliest index on ties)
+        auto seg_max = [&](unsigned lo, unsigned hi) {
+            const bool in = lane >= lo && lane < hi && live;
+            const double mx = az_wave_max(in ? el : -1.0e300);
+            const uint64_t hit = __ballot(in && el == mx);
+            if (hit && mx > best_el) {
+                best_el = mx;
+                best_i = base + (unsigned)__builtin_ctzll(hit);
+            }
+        };
+        uint64_t ev = rises | sets;
+        unsigned seg_lo = 0;
+        while (ev) {
+            const unsigned L = (unsigned)__builtin_ctzll(ev);
+            ev &= ev - 1u;
+            if (in_pass && L > seg_lo) seg_max(seg_lo, L);
+            const double t_e = az_readlane_f64(ev_t, L), az_e = az_readlane_f64(ev_az, L);
+            const unsigned fl_e = (unsigned)__builtin_amdgcn_readlane((int)ev_fl, (int)L);
+            if ((rises >> L) & 1u) {
+                in_pass = true;
+                cur = azh_pass{};
+                cur.t_rise_min = t_e;
+                cur.rise_azimuth_rad = az_e;
+                cur.flags = fl_e;
+                cur.grid_rise = base + L;
+                best_el = -1.0e300;
+                best_i = base + L;
+            } else {
+                cur.t_set_min = t_e;
+                cur.set_azimuth_rad = az_e;
+                cur.flags |= fl_e;
+                cur.grid_set = base + L - 1u;
+                finish();
+                in_pass = false;
+            }
+            seg_lo = L;
+        }
+        if (in_pass) seg_max(seg_lo, 64u);
+        carry_up = m >> 63;
+        carry_bad = mb >> 63;
+    }
+    if (in_pass) {
+        // still up at the last grid point
+        cur.t_set_min = T[n - 1];
+        cur.set_azimuth_rad = P[3 * (size_t)(n - 1)];
+        cur.flags |= AZH_PASS_UP_AT_END;
+        cur.grid_set = n - 1;
+        finish();
+    }
+    if (lane == 0) p.n_passes[srow] = count;
+}

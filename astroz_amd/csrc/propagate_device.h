@@ -790,3 +790,52 @@ AZ_DEVICE void az_ecef_to_geodetic(double p[3])
     p[1] = az_atan2(y, x);
     p[2] = rho * az_rcp(fmax(c, 6.123233995736766e-17)) - N; // (cos(pi/2) in fp64, the reference's divisor on the axis)
 }
+
+// Topocentric look angles (AZ_OUT_TOPOCENTRIC).  The observer record is built on the host once per call from geodetic WGS84
+// (lat, lon, alt), the ellipsoid az_ecef_to_geodetic uses: its ECEF position (km) and the (sin,cos) of latitude and longitude.
+struct AzObserver {
+    double x, y, z;
+    double sin_lat, cos_lat, sin_lon, cos_lon;
+};
+#define AZ_OMEGA_EARTH 7.292115146706979e-5 /* rad/s: Earth's rotation rate (the Earth-fixed relative velocity below) */
+// Conventions (the host twin azh_coords_topocentric follows them exactly):
+//   rho = r - r_obs in local East-North-Up components;
+//   positions slot  = (azimuth rad, elevation rad, range km): azimuth from north toward east in [0, 2 pi),
+//                     elevation = atan2(U, hypot(E, N));
+//   velocities slot = (azimuth rate rad/s, elevation rate rad/s, range rate km/s) of rho_dot = R v_teme - omega x r_ecef,
+//                     the Earth-fixed relative velocity (the ECEF output mode rotates the velocity only, like the reference;
+//                     the range rate here is the physical one a Doppler computation needs);
+//   hypot(E, N) < 1e-9 km (exactly overhead): azimuth, azimuth rate and elevation rate are 0.
+// r: ECEF position (already rotated by the kernels' Greenwich pair), v: the rotated velocity (read only when VEL).  Both are
+// overwritten with the two slots.
+template <bool VEL>
+AZ_DEVICE void az_topocentric(double r[3], double v[3], const AzObserver &o)
+{
+    const double dx = r[0] - o.x, dy = r[1] - o.y, dz = r[2] - o.z;
+    const double q = fma(o.cos_lon, dx, o.sin_lon * dy); // horizontal component in the observer's meridian plane
+    const double E = fma(o.cos_lon, dy, -(o.sin_lon * dx));
+    const double N = fma(o.cos_lat, dz, -(o.sin_lat * q));
+    const double U = fma(o.cos_lat, q, o.sin_lat * dz);
+    const double h2 = fma(E, E, N * N), r2 = fma(U, U, h2);
+    const double ih = az_rsqrt(fmax(h2, 1.0e-300)), ir = az_rsqrt(fmax(r2, 1.0e-300));
+    const double h = h2 * ih;
+    const bool overhead = h < 1.0e-9;
+    double az = az_atan2(E, N);
+    az = az < 0.0 ? az + AZ_TWOPI : az;
+    az = (overhead || az >= AZ_TWOPI) ? 0.0 : az;
+    if (VEL) {
+        const double vx = fma(AZ_OMEGA_EARTH, r[1], v[0]), vy = fma(-AZ_OMEGA_EARTH, r[0], v[1]), vz = v[2];
+        const double qd = fma(o.cos_lon, vx, o.sin_lon * vy);
+        const double Ed = fma(o.cos_lon, vy, -(o.sin_lon * vx));
+        const double Nd = fma(o.cos_lat, vz, -(o.sin_lat * qd));
+        const double Ud = fma(o.cos_lat, qd, o.sin_lat * vz);
+        const double hhd = fma(E, Ed, N * Nd); // h * dh/dt
+        const double ih2 = ih * ih, ir2 = ir * ir;
+        v[0] = overhead ? 0.0 : fma(Ed, N, -(E * Nd)) * ih2;
+        v[1] = overhead ? 0.0 : fma(h2, Ud, -(U * hhd)) * ih * ir2;
+        v[2] = fma(U, Ud, hhd) * ir;
+    }
+    r[0] = az;
+    r[1] = az_atan2(U, h);
+    r[2] = r2 * ir;
+}

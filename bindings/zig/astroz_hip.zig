@@ -142,6 +142,31 @@ pub extern "c" fn azh_selftest_coords(op: i32, in: *const [4]f64, out: *[5]f64) 
 pub extern "c" fn coords_julian_to_gmst(jd: f64) f64;
 pub extern "c" fn coords_eci_to_ecef(eci: *const [3]f64, gmst: f64, ecef: *[3]f64) void;
 pub extern "c" fn coords_ecef_to_geodetic(ecef: *const [3]f64, lla: *[3]f64) void;
+pub extern "c" fn azh_coords_topocentric(r_teme: *const [3]f64, v_teme: ?*const [3]f64, gmst: f64, observer_lla: *const [3]f64,
+    aer: *[3]f64, aer_rate: ?*[3]f64) void; // host twin of the AZ_OUT_TOPOCENTRIC epilogue
+
+// ground-station look angles (output_mode 3 = AZ_OUT_TOPOCENTRIC) and pass prediction
+pub const OUT_TOPOCENTRIC: i32 = 3;
+pub const Pass = extern struct {
+    t_rise_min: f64,
+    t_culm_min: f64,
+    t_set_min: f64,
+    max_elevation_rad: f64,
+    rise_azimuth_rad: f64,
+    set_azimuth_rad: f64,
+    flags: u32, // PASS_*
+    grid_rise: u32,
+    grid_culm: u32,
+    grid_set: u32,
+};
+pub const PASS_UP_AT_START: u32 = 1;
+pub const PASS_UP_AT_END: u32 = 2;
+pub const PASS_CUT_BY_ERROR: u32 = 4;
+pub extern "c" fn azh_set_observer(h: ?*Handle, lat_deg: f64, lon_deg: f64, alt_km: f64) i32;
+pub extern "c" fn azh_find_passes_host(h: ?*Handle, times_min: [*]const f64, n_times: usize, epoch_offsets_min: ?[*]const f64,
+    reference_jd: f64, min_elevation_deg: f64, out: [*]Pass, max_passes: usize, n_passes: [*]u32) i32;
+pub extern "c" fn azh_find_passes_device(h: ?*Handle, times_min: [*]const f64, n_times: usize, epoch_offsets_min: ?[*]const f64,
+    reference_jd: f64, min_elevation_deg: f64, d_out: [*]Pass, max_passes: usize, d_n_passes: [*]u32, stream: ?*anyopaque) i32;
 
 // one process, several devices: replaces the std.Thread fan-out of Constellation.propagateConstellation
 // (src/Constellation.zig L557-603)

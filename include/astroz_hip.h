@@ -47,8 +47,10 @@ enum {
 
 /* gravity model ids: bindings/python/src/shared.zig L21-27, src/c_api/sgp4.zig L17-20 */
 enum { AZ_WGS84 = 0, AZ_WGS72 = 1 };
-/* src/Constellation.zig L30-34 */
-enum { AZ_OUT_TEME = 0, AZ_OUT_ECEF = 1, AZ_OUT_GEODETIC = 2 };
+/* src/Constellation.zig L30-34; AZ_OUT_TOPOCENTRIC (no reference counterpart): look angles from the handle's observer
+ * (azh_set_observer) -- positions slot (azimuth rad from north toward east in [0, 2 pi), elevation rad, range km), velocities
+ * slot (azimuth rate rad/s, elevation rate rad/s, range rate km/s) of the Earth-fixed relative velocity (azh_coords_topocentric) */
+enum { AZ_OUT_TEME = 0, AZ_OUT_ECEF = 1, AZ_OUT_GEODETIC = 2, AZ_OUT_TOPOCENTRIC = 3 };
 /* src/Constellation.zig L37-42 */
 enum { AZ_LAYOUT_SAT_MAJOR = 0, AZ_LAYOUT_TIME_MAJOR = 1 };
 
@@ -87,6 +89,14 @@ int32_t sgp4_propagate_batch(void *handle, const double *times_min, double *resu
 double coords_julian_to_gmst(double jd);
 void coords_eci_to_ecef(const double eci[3], double gmst, double ecef[3]);
 void coords_ecef_to_geodetic(const double ecef[3], double lla[3]);
+/* Host twin of the kernels' topocentric epilogue (AZ_OUT_TOPOCENTRIC; no reference counterpart): TEME r (km) and v (km/s, may be
+ * NULL -> rates 0) at GMST gmst (rad), seen from observer_lla = (lat deg, lon deg, alt km) on WGS84 ->
+ * aer = (azimuth rad in [0, 2 pi) from north toward east, elevation rad, range km),
+ * aer_rate = (azimuth rate rad/s, elevation rate rad/s, range rate km/s) of rho_dot = R v - omega_earth x r_ecef
+ * (omega_earth = 7.292115146706979e-5 rad/s).  Exactly overhead (horizontal distance < 1e-9 km): azimuth and both angle rates
+ * are 0.  aer_rate may be NULL.  Pure host function. */
+void azh_coords_topocentric(const double r_teme[3], const double v_teme[3], double gmst, const double observer_lla[3],
+                            double aer[3], double aer_rate[3]);
 
 /* root.zig L60-71 / src/c_api/orbital_mechanics.zig: four closed-form scalars (src/calculations.zig L83-125) that are not on
  * the propagation path but belong to the reference's C surface, so that a client of libastroz_c.so links unchanged.  Same
@@ -236,6 +246,38 @@ int32_t azh_propagate_device_f32(azh_constellation *c, const double *times_min, 
                                  size_t out_stride_sats, uint8_t *d_err, void *stream);
 int32_t azh_propagate_device_cached_f32(azh_constellation *c, float *d_pos, float *d_vel, int32_t layout,
                                         size_t out_stride_sats, uint8_t *d_err, void *stream);
+
+/* Observer of AZ_OUT_TOPOCENTRIC and of the pass finder: geodetic WGS84, degrees / km.  |lat| > 90 or non-finite input ->
+ * AZ_ERR_VALUE (the previous observer stays).  Takes effect at the next launch, cached launches included; drops captured
+ * graphs.  AZ_OUT_TOPOCENTRIC on a handle without an observer is AZ_ERR_VALUE. */
+int32_t azh_set_observer(azh_constellation *c, double lat_deg, double lon_deg, double alt_km);
+
+/* Ground-station pass prediction (no reference counterpart): every satellite's passes above min_elevation_deg as seen from the
+ * handle's observer, over the grid times_min (strictly increasing, else AZ_ERR_VALUE; tsince and GMST as azh_propagate_*).
+ * The handle is propagated in AZ_OUT_TOPOCENTRIC with rates into a device scratch of at most ~512 MiB (row windows) and a
+ * kernel scans each row: up[i] = (no propagation error at i) && el[i] >= min_el; rises / sets are its 0 -> 1 / 1 -> 0
+ * transitions.  Rise and set times are the root of the cubic Hermite interpolant of elevation (values and rates at the two
+ * bracketing grid points) in that interval; the azimuths there are interpolated the same way; the culmination is the grid
+ * maximum of the pass, replaced by the highest point of the Hermite-interpolated topocentric (east, north, up) track on an
+ * adjacent interval where the elevation rate changes sign if that is higher.  Nothing is propagated again.
+ * out: n_sats x max_passes records, the first max_passes passes of satellite s at out[s * max_passes ...], in time order;
+ * n_passes[s] = the TRUE number of passes (may exceed max_passes).  grid_rise = first grid index of the pass, grid_set = its
+ * last, grid_culm = its grid maximum.  _device: out / n_passes on c's device, asynchronous on `stream` (NULL = the handle's). */
+typedef struct azh_pass {
+    double t_rise_min, t_culm_min, t_set_min; /* on the caller's time axis (times_min), refined (above) */
+    double max_elevation_rad, rise_azimuth_rad, set_azimuth_rad;
+    uint32_t flags;                           /* AZH_PASS_* */
+    uint32_t grid_rise, grid_culm, grid_set;  /* bracketing / maximal grid indices */
+} azh_pass;
+#define AZH_PASS_UP_AT_START 1u  /* visible at times_min[0]: rise = first grid time, not refined */
+#define AZH_PASS_UP_AT_END 2u    /* still visible at the last grid time: set = last grid time, not refined */
+#define AZH_PASS_CUT_BY_ERROR 4u /* begun or ended next to a grid point where propagation failed: that end is the grid time */
+int32_t azh_find_passes_host(azh_constellation *c, const double *times_min, size_t n_times, const double *epoch_offsets_min,
+                             double reference_jd, double min_elevation_deg, azh_pass *out, size_t max_passes,
+                             uint32_t *n_passes);
+int32_t azh_find_passes_device(azh_constellation *c, const double *times_min, size_t n_times, const double *epoch_offsets_min,
+                               double reference_jd, double min_elevation_deg, azh_pass *d_out, size_t max_passes,
+                               uint32_t *d_n_passes, void *stream);
 
 /* Fused single-target conjunction screen = Constellation.screenConstellation
  * (src/Constellation.zig L683-756; Python: Sgp4Constellation.screen_conjunction,
