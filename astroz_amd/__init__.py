@@ -328,6 +328,70 @@ def passes(source, times, observer, *, min_elevation=10.0, start_time=None, nora
 # passes(): one row per pass
 PASS_DTYPE = np.dtype([("sat", "<u4"), ("rise", "<f8"), ("culmination", "<f8"), ("set", "<f8"), ("max_elevation", "<f8"),
                        ("rise_azimuth", "<f8"), ("set_azimuth", "<f8"), ("flags", "<u4")])
+# station_passes(): one row per pass, with its station
+STATION_PASS_DTYPE = np.dtype([("station", "<u4")] + PASS_DTYPE.descr)
+# the records station_passes() asks one C call for (the stations are split over several calls beyond it; each repropagates)
+_STATION_CALL_BYTES = 256 << 20
+
+
+def station_passes(source, times, stations, *, min_elevation=10.0, start_time=None, norad_id=None, fetch=None,
+                   allow_network=False):
+    """Passes of every satellite over each of several ground stations, from one propagation of the catalog.
+
+    ``stations``: a sequence of ``(lat_deg, lon_deg, alt_km)`` (geodetic WGS84); ``min_elevation``: degrees, a scalar or one
+    value per station; ``times`` as for ``passes()`` (strictly increasing).  Returns a numpy structured array, one row per
+    pass, sorted by (station, sat, rise): ``station`` (index into ``stations``) and the fields of ``passes()``.  Station st's
+    rows are the passes ``passes(source, times, stations[st], min_elevation=...)`` finds (times and angles equal to within
+    the last bits); the constellation's own observer is not changed."""
+    try:
+        st = np.array([[float(x) for x in s] for s in stations], dtype=np.float64)
+    except (TypeError, ValueError):
+        st = None
+    if st is None or (st.size and (st.ndim != 2 or st.shape[1] != 3)):
+        raise ValueError("stations must be a sequence of (lat_deg, lon_deg, alt_km)")
+    st = st.reshape(-1, 3)
+    if not (np.isfinite(st).all() and (np.abs(st[:, 0]) <= 90.0).all()):
+        raise ValueError("stations must be finite with |lat_deg| <= 90")
+    mask = np.asarray(min_elevation, dtype=np.float64)
+    if mask.ndim == 0:
+        mask = np.full(len(st), float(mask))
+    if mask.shape != (len(st),):
+        raise ValueError("min_elevation must be a scalar or one value per station")
+    if not np.isfinite(mask).all():
+        raise ValueError("min_elevation must be finite")
+    minutes = np.ascontiguousarray(times, dtype=np.float64)
+    if minutes.ndim != 1 or (len(minutes) > 1 and not (np.diff(minutes) > 0).all()):
+        raise ValueError("times must be strictly increasing")
+    const = source if isinstance(source, Constellation) else Constellation(source, norad_id=norad_id, fetch=fetch,
+                                                                           allow_network=allow_network)
+    minutes, offsets, start = _minutes_and_offsets(const, minutes, start_time)
+    n = const.num_satellites
+    parts = []
+    room = 16
+    lo = 0
+    while lo < len(st):
+        # stations per call: their records within _STATION_CALL_BYTES
+        k = max(1, min(len(st) - lo, _STATION_CALL_BYTES // max(1, n * room * _native.PASS_DTYPE.itemsize)))
+        rec, cnt = const._dev.find_passes_stations(minutes, offsets, st[lo:lo + k], mask[lo:lo + k], reference_jd=start,
+                                                   max_passes=room)
+        if cnt.size and int(cnt.max()) > room:  # more passes than room: these stations once more with room for all of them
+            room = int(cnt.max())
+            k = max(1, min(k, _STATION_CALL_BYTES // max(1, n * room * _native.PASS_DTYPE.itemsize)))
+            rec, cnt = const._dev.find_passes_stations(minutes, offsets, st[lo:lo + k], mask[lo:lo + k], reference_jd=start,
+                                                       max_passes=room)
+        flat = cnt.reshape(-1)
+        idx = np.repeat(np.arange(flat.size, dtype=np.intp), flat)
+        kk = np.concatenate([np.arange(c, dtype=np.intp) for c in flat]) if flat.size else np.zeros(0, dtype=np.intp)
+        r = rec.reshape(-1, rec.shape[2])[idx, kk] if len(idx) else rec.reshape(-1)[:0]
+        out = np.empty(len(idx), dtype=STATION_PASS_DTYPE)
+        out["station"] = lo + idx // max(1, n)
+        out["sat"] = idx % max(1, n)
+        out["rise"], out["culmination"], out["set"] = r["t_rise_min"], r["t_culm_min"], r["t_set_min"]
+        out["max_elevation"], out["rise_azimuth"], out["set_azimuth"] = r["max_elevation_rad"], r["rise_azimuth_rad"], r["set_azimuth_rad"]
+        out["flags"] = r["flags"]
+        parts.append(out)
+        lo += k
+    return np.concatenate(parts) if parts else np.empty(0, dtype=STATION_PASS_DTYPE)
 
 
 def screen(source, times, threshold=10.0, *, target=None, start_time=None, norad_id=None, fetch=None, allow_network=False):
@@ -406,8 +470,8 @@ def escape_velocity(mu, radius):
     return _scalar(_native.lib().orbital_escape_velocity(float(mu), float(radius)), "orbital_escape_velocity", "invalid radius")
 
 
-__all__ = ["__version__", "Tle", "Sgp4Constellation", "Constellation", "propagate", "passes", "screen", "coarse_screen",
-           "set_fetcher", "celestrak_url", "WGS72", "WGS84", "hohmann_transfer", "orbital_velocity", "orbital_period",
+__all__ = ["__version__", "Tle", "Sgp4Constellation", "Constellation", "propagate", "passes", "station_passes", "screen",
+           "coarse_screen", "set_fetcher", "celestrak_url", "WGS72", "WGS84", "hohmann_transfer", "orbital_velocity", "orbital_period",
            "escape_velocity", "EARTH_MU", "EARTH_R_EQ", "EARTH_J2", "SUN_MU", "MOON_MU"]
 # (the reference's package also re-exports bi_elliptic_transfer, lambert and propagate_numerical -- its orbital-mechanics and
 # numerical-integration modules, outside the SGP4/SDP4 constellation path this package replaces: DESIGN.md 9)

@@ -46,7 +46,15 @@ EXPORTS = [
     "azh_group_shard_rows", "azh_group_synchronize", "azh_screen_track_device", "coords_eci_to_ecef", "coords_ecef_to_geodetic",
     "orbital_hohmann", "orbital_velocity", "orbital_period", "orbital_escape_velocity",
     "azh_coords_topocentric", "azh_set_observer", "azh_find_passes_host", "azh_find_passes_device",
+    "azh_find_passes_stations_host", "azh_find_passes_stations_device",
 ]
+
+
+def _stations(stations, min_elevation_deg):
+    """(S, 3) stations and (S,) masks as contiguous float64; a scalar mask applies to every station."""
+    st = np.ascontiguousarray(stations, dtype=np.float64).reshape(-1, 3)
+    mk = np.ascontiguousarray(np.broadcast_to(np.asarray(min_elevation_deg, dtype=np.float64), (len(st),)))
+    return st, mk
 
 
 class NativeError(RuntimeError):
@@ -251,6 +259,10 @@ def lib():
     L.azh_find_passes_host.restype = i32
     L.azh_find_passes_device.argtypes = [vp, vp, sz, vp, dbl, dbl, vp, sz, vp, vp]
     L.azh_find_passes_device.restype = i32
+    L.azh_find_passes_stations_host.argtypes = [vp, vp, sz, vp, dbl, vp, vp, sz, vp, sz, vp]
+    L.azh_find_passes_stations_host.restype = i32
+    L.azh_find_passes_stations_device.argtypes = [vp, vp, sz, vp, dbl, vp, vp, sz, vp, sz, vp, vp]
+    L.azh_find_passes_stations_device.restype = i32
     L.orbital_hohmann.argtypes = [dbl, dbl, dbl, vp]
     L.orbital_hohmann.restype = i32
     for f, n in (("orbital_velocity", 3), ("orbital_period", 2), ("orbital_escape_velocity", 2)):
@@ -479,6 +491,34 @@ class DeviceConstellation:
         check(lib().azh_find_passes_device(self._h, times.ctypes.data, len(times), _ptr(off), float(reference_jd),
                                            float(min_elevation_deg), d_out, int(max_passes), d_n_passes, stream),
               "azh_find_passes_device")
+
+    def find_passes_stations(self, times_min, offsets_min, stations, min_elevation_deg, *, reference_jd=0.0, max_passes=16):
+        """Passes over each of S ground stations in one propagation (azh_find_passes_stations_host): stations (S, 3)
+        (lat_deg, lon_deg, alt_km), min_elevation_deg (S,) -> (records (S, n, max_passes) of PASS_DTYPE, n_passes (S, n) u32
+        -- the TRUE counts).  The handle's observer is neither needed nor changed."""
+        times = _f64(times_min)
+        off = None if offsets_min is None else _f64(offsets_min)
+        if off is not None and len(off) < self.n:
+            raise ValueError("epoch_offsets must have at least num_satellites elements")
+        st, mk = _stations(stations, min_elevation_deg)
+        out = np.zeros((len(st), self.n, int(max_passes)), dtype=PASS_DTYPE)
+        cnt = np.zeros((len(st), self.n), dtype=np.uint32)
+        check(lib().azh_find_passes_stations_host(self._h, times.ctypes.data, len(times), _ptr(off), float(reference_jd),
+                                                  st.ctypes.data, mk.ctypes.data, len(st),
+                                                  out.ctypes.data if max_passes else None, int(max_passes), cnt.ctypes.data),
+              "azh_find_passes_stations_host")
+        return out, cnt
+
+    def find_passes_stations_device(self, times_min, offsets_min, stations, min_elevation_deg, d_out, max_passes, d_n_passes, *,
+                                    reference_jd=0.0, stream=None):
+        """azh_find_passes_stations_device: d_out / d_n_passes are raw device pointers (S x n x max_passes records of
+        PASS_DTYPE, S x n u32); asynchronous."""
+        times = _f64(times_min)
+        off = None if offsets_min is None else _f64(offsets_min)
+        st, mk = _stations(stations, min_elevation_deg)
+        check(lib().azh_find_passes_stations_device(self._h, times.ctypes.data, len(times), _ptr(off), float(reference_jd),
+                                                    st.ctypes.data, mk.ctypes.data, len(st), d_out, int(max_passes), d_n_passes,
+                                                    stream), "azh_find_passes_stations_device")
 
     def screen_all(self, times_min, threshold=10.0, offsets_min=None, max_results=10_000_000):
         """All-vs-all: propagate on the device and screen there: (pairs (k,2) u32, t_index (k,) u32),

@@ -255,6 +255,8 @@ struct azh_constellation {
     DevBuf<unsigned char> d_pass_err;
     DevBuf<azh_pass> d_pass_out;          // ... and the records / counts of azh_find_passes_host
     DevBuf<uint32_t> d_pass_n;
+    std::vector<AzStation> h_stations;    // azh_find_passes_stations_*: the stations of the last call ...
+    DevBuf<AzStation> d_stations;         // ... and their grow-only device copy
     unsigned cached_n_times = 0;
     int cached_mode = 0;
     unsigned off_cat = 0; // d_list + off_cat: near-earth members in plain catalog order (k_tiles_fast: runs of consecutive rows)
@@ -2598,6 +2600,121 @@ int32_t azh_find_passes_host(azh_constellation *c, const double *times, size_t n
         int32_t rc = find_passes(c, times, n_times, offsets, reference_jd, min_elevation_deg, n_rec ? c->d_pass_out.p : nullptr, max_passes,
                                  c->d_pass_n.p, c->s_main);
         if (rc == AZ_OK && !hip_ok(hipMemcpyAsync(n_passes, c->d_pass_n.p, sizeof(uint32_t) * c->n, hipMemcpyDeviceToHost, c->s_main), "D2H"))
+            rc = AZ_ERR_HIP;
+        if (rc == AZ_OK && n_rec &&
+            !hip_ok(hipMemcpyAsync(out, c->d_pass_out.p, sizeof(azh_pass) * n_rec, hipMemcpyDeviceToHost, c->s_main), "D2H"))
+            rc = AZ_ERR_HIP;
+        if (!hip_ok(hipStreamSynchronize(c->s_main), "sync") && rc == AZ_OK) rc = AZ_ERR_HIP;
+        return rc;
+    });
+}
+
+// azh_find_passes_stations_*: propagate to AZ_OUT_ECEF with velocities, satellite-major, into the same scratch one row window
+// at a time, and scan every window's rows with k_passes_stations once per group of AZ_STATION_GROUP stations: the propagation
+// does not depend on the station, and a group reads the scratch once.
+static int32_t find_passes_stations(azh_constellation *c, const double *times, size_t n_times, const double *offsets,
+                                    double reference_jd, const double *lla, const double *mask_deg, size_t n_st, azh_pass *d_out,
+                                    size_t max_passes, uint32_t *d_n, hipStream_t st)
+{
+    if (n_st == 0 || c->n == 0) return AZ_OK;
+    if (!c->h_stations.empty() && c->d_stations.cap < n_st) HIP_TRY(hipStreamSynchronize(st)); // (a scan in flight reads it)
+    if (c->d_stations.ensure(n_st) != AZ_OK) return AZ_ERR_HIP;
+    c->h_stations.resize(n_st);
+    for (size_t k = 0; k < n_st; ++k) {
+        AzStation &S = c->h_stations[k];
+        S.o = make_observer(lla[3 * k], lla[3 * k + 1], lla[3 * k + 2]);
+        S.min_el = mask_deg[k] * (AZ_PI / 180.0); // (k_passes's arithmetic)
+        S.s2 = std::sin(S.min_el) * std::fabs(std::sin(S.min_el));
+    }
+    HIP_TRY(hipMemcpyAsync(c->d_stations.p, c->h_stations.data(), sizeof(AzStation) * n_st, hipMemcpyHostToDevice, st));
+    if (n_times == 0) {
+        HIP_TRY(hipMemsetAsync(d_n, 0, sizeof(uint32_t) * c->n * n_st, st));
+        return AZ_OK;
+    }
+    if (int32_t rc = stage_inputs(c, times, n_times, offsets, nullptr, AZ_OUT_ECEF, reference_jd, st); rc != AZ_OK) return rc;
+    const size_t per_row = n_times * (6 * sizeof(double) + 1);
+    const size_t rows_w = std::max<size_t>(1, std::min(c->n, kPassScratch / per_row));
+    const size_t words = rows_w * n_times * 3;
+    if (c->d_pass_pos.cap < words || c->d_pass_vel.cap < words || c->d_pass_err.cap < rows_w * n_times)
+        HIP_TRY(hipStreamSynchronize(st)); // (launches in flight use the old buffers)
+    if (c->d_pass_pos.ensure(words) != AZ_OK || c->d_pass_vel.ensure(words) != AZ_OK || c->d_pass_err.ensure(rows_w * n_times) != AZ_OK)
+        return AZ_ERR_HIP;
+    for (size_t lo = 0; lo < c->n; lo += rows_w) {
+        const size_t hi = std::min(c->n, lo + rows_w);
+        const size_t shift = lo * n_times; // (the window's rows land at the start of the scratch, as in find_passes)
+        const uintptr_t pb = reinterpret_cast<uintptr_t>(c->d_pass_pos.p) - 3 * shift * sizeof(double);
+        const uintptr_t vb = reinterpret_cast<uintptr_t>(c->d_pass_vel.p) - 3 * shift * sizeof(double);
+        const uintptr_t eb = reinterpret_cast<uintptr_t>(c->d_pass_err.p) - shift;
+        if (int32_t rc = launch_all(c, reinterpret_cast<double *>(pb), reinterpret_cast<double *>(vb), AZ_LAYOUT_SAT_MAJOR, 0,
+                                    reinterpret_cast<uint8_t *>(eb), st, 0, lo, hi);
+            rc != AZ_OK)
+            return rc;
+        for (size_t g = 0; g < n_st; g += AZ_STATION_GROUP) {
+            StationPassArgs q{};
+            q.pos = c->d_pass_pos.p; q.vel = c->d_pass_vel.p; q.err = c->d_pass_err.p;
+            q.times = c->d_times.p; q.n_times = (unsigned)n_times;
+            q.row0 = (unsigned)lo; q.n_rows = (unsigned)(hi - lo); q.n_sats = (unsigned)c->n;
+            q.st = c->d_stations.p + g; q.n_st = (unsigned)std::min<size_t>(AZ_STATION_GROUP, n_st - g); q.st0 = (unsigned)g;
+            q.out = d_out; q.max_passes = (unsigned)max_passes; q.n_passes = d_n;
+            hipLaunchKernelGGL(k_passes_stations, dim3((unsigned)((hi - lo + AZ_PASS_WAVES - 1) / AZ_PASS_WAVES)), dim3(64 * AZ_PASS_WAVES),
+                               0, st, q);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    return AZ_OK;
+}
+
+// the argument rules of both variants, checked before the device is touched; n_rec = the records out holds
+static int32_t stations_args(const azh_constellation *c, const double *times, size_t n_times, const double *lla, const double *mask_deg,
+                             size_t n_st, size_t max_passes, size_t &n_rec)
+{
+    if (max_passes > 0xffffffffu || n_st > 0xffffffffu) return AZ_ERR_VALUE;
+    size_t rows, bytes;
+    if (__builtin_mul_overflow(n_st, c->n, &rows) || __builtin_mul_overflow(rows, max_passes, &n_rec) ||
+        __builtin_mul_overflow(n_rec, sizeof(azh_pass), &bytes) || __builtin_mul_overflow(rows, sizeof(uint32_t), &bytes))
+        return AZ_ERR_VALUE;
+    for (size_t k = 0; k < n_st; ++k)
+        if (!observer_ok(lla[3 * k], lla[3 * k + 1], lla[3 * k + 2]) || !std::isfinite(mask_deg[k])) return AZ_ERR_VALUE;
+    for (size_t i = 1; i < n_times; ++i)
+        if (!(times[i] > times[i - 1])) return AZ_ERR_VALUE; // (the Hermite interval needs a length > 0; NaN fails too)
+    return AZ_OK;
+}
+
+int32_t azh_find_passes_stations_device(azh_constellation *c, const double *times, size_t n_times, const double *offsets,
+                                        double reference_jd, const double *stations_lla, const double *min_elevation_deg,
+                                        size_t n_stations, azh_pass *d_out, size_t max_passes, uint32_t *d_n_passes, void *stream)
+{
+    return guarded([&]() -> int32_t {
+        if (!c || !d_n_passes || (n_times && !times) || (n_stations && (!stations_lla || !min_elevation_deg)) || (max_passes && !d_out))
+            return AZ_ERR_NULL_POINTER;
+        size_t n_rec = 0;
+        if (int32_t rc = stations_args(c, times, n_times, stations_lla, min_elevation_deg, n_stations, max_passes, n_rec); rc != AZ_OK)
+            return rc;
+        if (n_stations == 0) return AZ_OK;
+        if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
+        return find_passes_stations(c, times, n_times, offsets, reference_jd, stations_lla, min_elevation_deg, n_stations, d_out,
+                                    max_passes, d_n_passes, stream ? (hipStream_t)stream : c->s_main);
+    });
+}
+
+int32_t azh_find_passes_stations_host(azh_constellation *c, const double *times, size_t n_times, const double *offsets,
+                                      double reference_jd, const double *stations_lla, const double *min_elevation_deg,
+                                      size_t n_stations, azh_pass *out, size_t max_passes, uint32_t *n_passes)
+{
+    return guarded([&]() -> int32_t {
+        if (!c || !n_passes || (n_times && !times) || (n_stations && (!stations_lla || !min_elevation_deg)) || (max_passes && !out))
+            return AZ_ERR_NULL_POINTER;
+        size_t n_rec = 0;
+        if (int32_t rc = stations_args(c, times, n_times, stations_lla, min_elevation_deg, n_stations, max_passes, n_rec); rc != AZ_OK)
+            return rc;
+        if (n_stations == 0 || c->n == 0) return AZ_OK;
+        if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
+        const size_t n_cnt = c->n * n_stations;
+        if (c->d_pass_out.cap < n_rec || c->d_pass_n.cap < n_cnt) HIP_TRY(hipStreamSynchronize(c->s_main));
+        if ((n_rec && c->d_pass_out.ensure(n_rec) != AZ_OK) || c->d_pass_n.ensure(n_cnt) != AZ_OK) return AZ_ERR_HIP;
+        int32_t rc = find_passes_stations(c, times, n_times, offsets, reference_jd, stations_lla, min_elevation_deg, n_stations,
+                                          n_rec ? c->d_pass_out.p : nullptr, max_passes, c->d_pass_n.p, c->s_main);
+        if (rc == AZ_OK && !hip_ok(hipMemcpyAsync(n_passes, c->d_pass_n.p, sizeof(uint32_t) * n_cnt, hipMemcpyDeviceToHost, c->s_main), "D2H"))
             rc = AZ_ERR_HIP;
         if (rc == AZ_OK && n_rec &&
             !hip_ok(hipMemcpyAsync(out, c->d_pass_out.p, sizeof(azh_pass) * n_rec, hipMemcpyDeviceToHost, c->s_main), "D2H"))

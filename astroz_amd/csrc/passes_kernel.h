@@ -276,3 +276,246 @@ __global__ void __launch_bounds__(64 * AZ_PASS_WAVES) k_passes(PassArgs p)
     }
     if (lane == 0) p.n_passes[srow] = count;
 }
+
+// ---- several stations per call (azh_find_passes_stations_*) -------------------------------------------------------------
+// Input: one row window of AZ_OUT_ECEF output with velocities, satellite-major -- per row and grid point the Earth-fixed
+// position, the rotated velocity and the propagation error code -- and a group of at most 64 stations.  Same mapping as
+// k_passes (one wave per row, lanes on 64 consecutive grid points); each chunk's state is loaded once and the stations are
+// walked inside the time loop.  Every elevation, azimuth and rate that enters a decision or a record is az_topocentric<true>
+// of the stored state, the arithmetic k_rows_fast FRAME 3 applies to the same rotated state, so that a station's records are
+// those of k_passes for it.  The up test is first decided without atan2: el >= min_el <=> U |U| >= s |s| |rho|^2
+// (s = sin(min_el)); within a relative margin of 1e-12 of |rho|^2 -- far above the rounding of either side -- the exact
+// elevation decides.  A chunk with no up lane and no pass under way costs that test only.  The state of station j's pass
+// (count, record under way, running maximum) lives in lane j and is read into wave-uniform registers with readlane when the
+// station has anything to do in a chunk; whether its pass is under way is bit j of a wave-uniform mask.
+struct AzStation {
+    AzObserver o;
+    double min_el; // rad
+    double s2;     // sin(min_el) |sin(min_el)|
+};
+
+#define AZ_STATION_GROUP 64
+struct StationPassArgs {
+    const double *pos, *vel;  // [row - row0][n_times][3]: ECEF position, rotated velocity
+    const unsigned char *err; // [row - row0][n_times]
+    const double *times;      // the caller's time axis (minutes), strictly increasing
+    unsigned n_times;
+    unsigned row0, n_rows; // catalog rows [row0, row0 + n_rows) of this window
+    unsigned n_sats;       // catalog rows in all: the station stride of out / n_passes
+    const AzStation *st;   // this group's stations ...
+    unsigned n_st, st0;    // ... n_st <= AZ_STATION_GROUP of them, the first being station st0 of the call
+    azh_pass *out;         // [n_stations][n_sats][max_passes]
+    unsigned max_passes;
+    uint32_t *n_passes; // [n_stations][n_sats]
+};
+
+// look angles and their rates of grid point i from observer o
+__device__ __forceinline__ void az_look(const double *P, const double *V, size_t i, const AzObserver &o, double a[3], double ad[3])
+{
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        a[k] = P[3 * i + k];
+        ad[k] = V[3 * i + k];
+    }
+    az_topocentric<true>(a, ad, o);
+}
+
+// one station's pass under way, and what it has stored
+struct AzPassState {
+    azh_pass cur;
+    double best_el;
+    unsigned best_i, count;
+};
+__device__ __forceinline__ unsigned az_readlane_u32(unsigned x, unsigned l) { return (unsigned)__builtin_amdgcn_readlane((int)x, (int)l); }
+__device__ __forceinline__ AzPassState az_state_of(const AzPassState &s, unsigned l)
+{
+    AzPassState u;
+    u.cur.t_rise_min = az_readlane_f64(s.cur.t_rise_min, l);
+    u.cur.t_culm_min = az_readlane_f64(s.cur.t_culm_min, l);
+    u.cur.t_set_min = az_readlane_f64(s.cur.t_set_min, l);
+    u.cur.max_elevation_rad = az_readlane_f64(s.cur.max_elevation_rad, l);
+    u.cur.rise_azimuth_rad = az_readlane_f64(s.cur.rise_azimuth_rad, l);
+    u.cur.set_azimuth_rad = az_readlane_f64(s.cur.set_azimuth_rad, l);
+    u.cur.flags = az_readlane_u32(s.cur.flags, l);
+    u.cur.grid_rise = az_readlane_u32(s.cur.grid_rise, l);
+    u.cur.grid_culm = az_readlane_u32(s.cur.grid_culm, l);
+    u.cur.grid_set = az_readlane_u32(s.cur.grid_set, l);
+    u.best_el = az_readlane_f64(s.best_el, l);
+    u.best_i = az_readlane_u32(s.best_i, l);
+    u.count = az_readlane_u32(s.count, l);
+    return u;
+}
+
+__global__ void __launch_bounds__(64 * AZ_PASS_WAVES) k_passes_stations(StationPassArgs p)
+{
+    const unsigned lane = threadIdx.x & 63u;
+    const unsigned wrow = blockIdx.x * AZ_PASS_WAVES + (threadIdx.x >> 6);
+    if (wrow >= p.n_rows) return; // (wave-uniform)
+    const unsigned n = p.n_times;
+    const double *P = p.pos + (size_t)wrow * n * 3, *V = p.vel + (size_t)wrow * n * 3;
+    const unsigned char *E = p.err + (size_t)wrow * n;
+    const double *T = p.times;
+    const size_t srow = (size_t)p.row0 + wrow;
+
+    AzPassState mine{};      // station `lane`'s
+    mine.best_el = -1.0e300;
+    uint64_t in_pass_mask = 0; // bit j: station j has a pass under way (its last grid point was up)
+    uint64_t carry_bad = 0;    // the grid point before this iteration's first failed
+
+    // the record of a pass whose set is known: culmination refinement, store (the first max_passes only)
+    auto finish = [&](const AzStation &S, AzPassState &u, unsigned j) {
+        double t_c = T[u.best_i], e_c = u.best_el;
+        const unsigned k = u.best_i;
+#pragma unroll
+        for (int side = 0; side < 2; ++side) {
+            if (side == 0 && k == 0) continue;
+            if (side == 1 && k + 1 >= n) continue;
+            const unsigned i0 = side == 0 ? k - 1 : k, i1 = i0 + 1;
+            if (E[i0] != 0 || E[i1] != 0) continue;
+            double a0[3], d0[3], a1[3], d1[3];
+            az_look(P, V, i0, S.o, a0, d0);
+            az_look(P, V, i1, S.o, a1, d1);
+            if (!(d0[1] > 0.0 && d1[1] < 0.0)) continue;
+            const double dt = T[i1] - T[i0];
+            double s;
+            const double e = az_culmination(a0, d0, a1, d1, dt, s);
+            if (e > e_c) {
+                e_c = e;
+                t_c = fma(s, dt, T[i0]);
+            }
+        }
+        u.cur.t_culm_min = t_c;
+        u.cur.max_elevation_rad = e_c;
+        u.cur.grid_culm = k;
+        if (lane == 0 && u.count < p.max_passes) p.out[((size_t)(p.st0 + j) * p.n_sats + srow) * p.max_passes + u.count] = u.cur;
+        ++u.count;
+    };
+
+    for (unsigned base = 0; base < n; base += 64) {
+        const unsigned i = base + lane;
+        const bool live = i < n;
+        double r[3] = {0.0, 0.0, 0.0};
+        bool bad = false;
+        if (live) {
+            r[0] = P[3 * (size_t)i];
+            r[1] = P[3 * (size_t)i + 1];
+            r[2] = P[3 * (size_t)i + 2];
+            bad = E[i] != 0;
+        }
+        const bool ok = live && !bad;
+        const uint64_t mb = __ballot(bad), ml = __ballot(live);
+        const uint64_t prevb = (mb << 1) | carry_bad;
+        for (unsigned j = 0; j < p.n_st; ++j) {
+            const AzStation S = p.st[j]; // (wave-uniform)
+            const bool was_in = (in_pass_mask >> j) & 1u;
+            // the cheap test: U |U| against s |s| |rho|^2, exact elevation near the mask
+            const double dx = r[0] - S.o.x, dy = r[1] - S.o.y, dz = r[2] - S.o.z;
+            const double q = fma(S.o.cos_lon, dx, S.o.sin_lon * dy);
+            const double U = fma(S.o.cos_lat, q, S.o.sin_lat * dz);
+            const double rho2 = fma(dx, dx, fma(dy, dy, dz * dz));
+            const double d = fma(U, fabs(U), -(S.s2 * rho2)), margin = 1.0e-12 * rho2;
+            if (!was_in && !az_any(ok && d >= -margin)) continue; // nothing up, nothing under way
+            double el = 0.0;
+            if (ok) {
+                double a[3] = {r[0], r[1], r[2]}, ad[3] = {0.0, 0.0, 0.0}; // (the position slot does not read the velocity)
+                az_topocentric<true>(a, ad, S.o);
+                el = a[1];
+            }
+            const bool up = ok && el >= S.min_el;
+            const uint64_t m = __ballot(up);
+            if (!was_in && m == 0) continue;
+
+            AzPassState u = az_state_of(mine, j);
+            bool in_pass = was_in;
+            const uint64_t prev = (m << 1) | (uint64_t)was_in;
+            const uint64_t rises = m & ~prev, sets = ~m & prev & ml;
+            const bool is_rise = (rises >> lane) & 1u, is_set = (sets >> lane) & 1u;
+            // refinement by the lane that owns the event, as k_passes
+            double ev_t = 0.0, ev_az = 0.0;
+            unsigned ev_fl = 0;
+            if (is_rise || is_set) {
+                const bool prev_bad = (prevb >> lane) & 1u;
+                if (is_rise && i == 0) {
+                    double a[3], ad[3];
+                    az_look(P, V, 0, S.o, a, ad);
+                    ev_t = T[0];
+                    ev_az = a[0];
+                    ev_fl = AZH_PASS_UP_AT_START;
+                } else if ((is_rise && prev_bad) || (is_set && bad)) {
+                    const unsigned jj = is_rise ? i : i - 1; // the open end stays on the grid point that propagated
+                    double a[3], ad[3];
+                    az_look(P, V, jj, S.o, a, ad);
+                    ev_t = T[jj];
+                    ev_az = a[0];
+                    ev_fl = AZH_PASS_CUT_BY_ERROR;
+                } else {
+                    const unsigned i0 = i - 1;
+                    double a0[3], d0[3], a1[3], d1[3];
+                    az_look(P, V, i0, S.o, a0, d0);
+                    az_look(P, V, i, S.o, a1, d1);
+                    const double dt = T[i] - T[i0];
+                    const double f0 = a0[1] - S.min_el, f1 = a1[1] - S.min_el;
+                    const double s = az_herm_root(f0, f1, 60.0 * dt * d0[1], 60.0 * dt * d1[1]);
+                    ev_t = fma(s, dt, T[i0]);
+                    ev_az = az_herm_azimuth(a0[0], a1[0], 60.0 * dt * d0[0], 60.0 * dt * d1[0], s);
+                }
+            }
+            // the segment [lo, hi) of this iteration belongs to the pass under way: its grid maximum (earliest index on ties)
+            auto seg_max = [&](unsigned lo, unsigned hi) {
+                const bool in = lane >= lo && lane < hi && live;
+                const double mx = az_wave_max(in ? el : -1.0e300);
+                const uint64_t hit = __ballot(in && el == mx);
+                if (hit && mx > u.best_el) {
+                    u.best_el = mx;
+                    u.best_i = base + (unsigned)__builtin_ctzll(hit);
+                }
+            };
+            uint64_t ev = rises | sets;
+            unsigned seg_lo = 0;
+            while (ev) {
+                const unsigned L = (unsigned)__builtin_ctzll(ev);
+                ev &= ev - 1u;
+                if (in_pass && L > seg_lo) seg_max(seg_lo, L);
+                const double t_e = az_readlane_f64(ev_t, L), az_e = az_readlane_f64(ev_az, L);
+                const unsigned fl_e = az_readlane_u32(ev_fl, L);
+                if ((rises >> L) & 1u) {
+                    in_pass = true;
+                    u.cur = azh_pass{};
+                    u.cur.t_rise_min = t_e;
+                    u.cur.rise_azimuth_rad = az_e;
+                    u.cur.flags = fl_e;
+                    u.cur.grid_rise = base + L;
+                    u.best_el = -1.0e300;
+                    u.best_i = base + L;
+                } else {
+                    u.cur.t_set_min = t_e;
+                    u.cur.set_azimuth_rad = az_e;
+                    u.cur.flags |= fl_e;
+                    u.cur.grid_set = base + L - 1u;
+                    finish(S, u, j);
+                    in_pass = false;
+                }
+                seg_lo = L;
+            }
+            if (in_pass) seg_max(seg_lo, 64u);
+            if (lane == j) mine = u;
+            in_pass_mask = in_pass ? (in_pass_mask | (1ull << j)) : (in_pass_mask & ~(1ull << j));
+        }
+        carry_bad = mb >> 63;
+    }
+    // still up at the last grid point
+    for (uint64_t open = in_pass_mask; open; open &= open - 1u) {
+        const unsigned j = (unsigned)__builtin_ctzll(open);
+        const AzStation S = p.st[j];
+        AzPassState u = az_state_of(mine, j);
+        double a[3], ad[3];
+        az_look(P, V, n - 1, S.o, a, ad);
+        u.cur.t_set_min = T[n - 1];
+        u.cur.set_azimuth_rad = a[0];
+        u.cur.flags |= AZH_PASS_UP_AT_END;
+        u.cur.grid_set = n - 1;
+        finish(S, u, j);
+        if (lane == j) mine = u;
+    }
+    if (lane < p.n_st) p.n_passes[(size_t)(p.st0 + lane) * p.n_sats + srow] = mine.count;
+}

@@ -167,6 +167,12 @@ pub extern "c" fn azh_find_passes_host(h: ?*Handle, times_min: [*]const f64, n_t
     reference_jd: f64, min_elevation_deg: f64, out: [*]Pass, max_passes: usize, n_passes: [*]u32) i32;
 pub extern "c" fn azh_find_passes_device(h: ?*Handle, times_min: [*]const f64, n_times: usize, epoch_offsets_min: ?[*]const f64,
     reference_jd: f64, min_elevation_deg: f64, d_out: [*]Pass, max_passes: usize, d_n_passes: [*]u32, stream: ?*anyopaque) i32;
+pub extern "c" fn azh_find_passes_stations_host(h: ?*Handle, times_min: [*]const f64, n_times: usize,
+    epoch_offsets_min: ?[*]const f64, reference_jd: f64, stations_lla: [*]const [3]f64, min_elevation_deg: [*]const f64,
+    n_stations: usize, out: [*]Pass, max_passes: usize, n_passes: [*]u32) i32;
+pub extern "c" fn azh_find_passes_stations_device(h: ?*Handle, times_min: [*]const f64, n_times: usize,
+    epoch_offsets_min: ?[*]const f64, reference_jd: f64, stations_lla: [*]const [3]f64, min_elevation_deg: [*]const f64,
+    n_stations: usize, d_out: [*]Pass, max_passes: usize, d_n_passes: [*]u32, stream: ?*anyopaque) i32;
 
 // one process, several devices: replaces the std.Thread fan-out of Constellation.propagateConstellation
 // (src/Constellation.zig L557-603)

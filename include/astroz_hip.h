@@ -279,6 +279,24 @@ int32_t azh_find_passes_device(azh_constellation *c, const double *times_min, si
                                double reference_jd, double min_elevation_deg, azh_pass *d_out, size_t max_passes,
                                uint32_t *d_n_passes, void *stream);
 
+/* Passes of every satellite over each of n_stations ground stations, in one propagation of the handle (no reference
+ * counterpart).  stations_lla: n_stations x 3 (lat_deg, lon_deg, alt_km), geodetic WGS84, validated like azh_set_observer;
+ * min_elevation_deg: n_stations masks (degrees, finite).  Host arrays in both variants.  Any invalid station or mask ->
+ * AZ_ERR_VALUE and nothing is launched; n_stations == 0 -> AZ_OK, nothing done; max_passes == 0 -> counts only.
+ * out: n_stations x n_sats x max_passes records; out[(st * n_sats + s) * max_passes + k] is the k-th pass of satellite s over
+ * station st, in time order.  n_passes: n_stations x n_sats TRUE counts (may exceed max_passes).
+ * The slice for station st is what azh_find_passes_* writes after azh_set_observer(st) with the same mask: the handle is
+ * propagated once per row window in AZ_OUT_ECEF with velocities, and every station's look angles are the topocentric
+ * epilogue's arithmetic on that state.  The handle's own observer is neither needed nor changed.  _device: out / n_passes on
+ * c's device, asynchronous on `stream` (NULL = the handle's). */
+int32_t azh_find_passes_stations_host(azh_constellation *c, const double *times_min, size_t n_times, const double *epoch_offsets_min,
+                                      double reference_jd, const double *stations_lla, const double *min_elevation_deg,
+                                      size_t n_stations, azh_pass *out, size_t max_passes, uint32_t *n_passes);
+int32_t azh_find_passes_stations_device(azh_constellation *c, const double *times_min, size_t n_times,
+                                        const double *epoch_offsets_min, double reference_jd, const double *stations_lla,
+                                        const double *min_elevation_deg, size_t n_stations, azh_pass *d_out, size_t max_passes,
+                                        uint32_t *d_n_passes, void *stream);
+
 /* Fused single-target conjunction screen = Constellation.screenConstellation
  * (src/Constellation.zig L683-756; Python: Sgp4Constellation.screen_conjunction,
  * bindings/python/astroz/__init__.py L625-632).  For every satellite the minimum distance (km) to
