@@ -314,15 +314,22 @@ def passes(source, times, observer, *, min_elevation=10.0, start_time=None, nora
     if cnt.size and int(cnt.max()) > rec.shape[1]:  # more passes than room: once more with room for all of them
         rec, cnt = const._dev.find_passes(minutes, offsets, reference_jd=start, min_elevation_deg=float(min_elevation),
                                           max_passes=int(cnt.max()))
-    sat = np.repeat(np.arange(len(cnt), dtype=np.uint32), cnt)
+    idx, out = _pass_rows(rec, cnt, PASS_DTYPE)
+    out["sat"] = idx
+    return out
+
+
+def _pass_rows(rec, cnt, dtype):
+    """The passes of records ``rec`` (rows, max_passes) with counts ``cnt`` (rows,), one per row of a new ``dtype`` array in
+    (row, k) order with the ``PASS_DTYPE`` fields filled, and the row index of each."""
+    idx = np.repeat(np.arange(len(cnt), dtype=np.intp), cnt)
     k = np.concatenate([np.arange(c, dtype=np.intp) for c in cnt]) if len(cnt) else np.zeros(0, dtype=np.intp)
-    r = rec[sat, k] if len(sat) else rec.reshape(-1)[:0]
-    out = np.empty(len(sat), dtype=PASS_DTYPE)
-    out["sat"] = sat
+    r = rec[idx, k] if len(idx) else rec.reshape(-1)[:0]
+    out = np.empty(len(idx), dtype=dtype)
     out["rise"], out["culmination"], out["set"] = r["t_rise_min"], r["t_culm_min"], r["t_set_min"]
     out["max_elevation"], out["rise_azimuth"], out["set_azimuth"] = r["max_elevation_rad"], r["rise_azimuth_rad"], r["set_azimuth_rad"]
     out["flags"] = r["flags"]
-    return out
+    return idx, out
 
 
 # passes(): one row per pass
@@ -379,16 +386,9 @@ def station_passes(source, times, stations, *, min_elevation=10.0, start_time=No
             k = max(1, min(k, _STATION_CALL_BYTES // max(1, n * room * _native.PASS_DTYPE.itemsize)))
             rec, cnt = const._dev.find_passes_stations(minutes, offsets, st[lo:lo + k], mask[lo:lo + k], reference_jd=start,
                                                        max_passes=room)
-        flat = cnt.reshape(-1)
-        idx = np.repeat(np.arange(flat.size, dtype=np.intp), flat)
-        kk = np.concatenate([np.arange(c, dtype=np.intp) for c in flat]) if flat.size else np.zeros(0, dtype=np.intp)
-        r = rec.reshape(-1, rec.shape[2])[idx, kk] if len(idx) else rec.reshape(-1)[:0]
-        out = np.empty(len(idx), dtype=STATION_PASS_DTYPE)
+        idx, out = _pass_rows(rec.reshape(-1, rec.shape[2]), cnt.reshape(-1), STATION_PASS_DTYPE)
         out["station"] = lo + idx // max(1, n)
         out["sat"] = idx % max(1, n)
-        out["rise"], out["culmination"], out["set"] = r["t_rise_min"], r["t_culm_min"], r["t_set_min"]
-        out["max_elevation"], out["rise_azimuth"], out["set_azimuth"] = r["max_elevation_rad"], r["rise_azimuth_rad"], r["set_azimuth_rad"]
-        out["flags"] = r["flags"]
         parts.append(out)
         lo += k
     return np.concatenate(parts) if parts else np.empty(0, dtype=STATION_PASS_DTYPE)

@@ -2531,21 +2531,28 @@ int32_t azh_set_observer(azh_constellation *c, double lat_deg, double lon_deg, d
     });
 }
 
-// azh_find_passes_*: propagate to AZ_OUT_TOPOCENTRIC with rates, satellite-major, into the handle's scratch one row window at a
-// time (at most kPassScratch bytes: pos + vel + err), and scan every window's rows with k_passes behind its propagation
-static constexpr size_t kPassScratch = size_t(512) << 20;
-static int32_t find_passes(azh_constellation *c, const double *times, size_t n_times, const double *offsets, double reference_jd,
-                           double min_elevation_deg, azh_pass *d_out, size_t max_passes, uint32_t *d_n, hipStream_t st)
+// the time axis of a pass search: strictly increasing (the Hermite interval needs a length > 0; NaN fails too)
+static bool times_increasing(const double *times, size_t n)
 {
-    if (!c->have_observer || !std::isfinite(min_elevation_deg) || max_passes > 0xffffffffu) return AZ_ERR_VALUE;
-    for (size_t i = 1; i < n_times; ++i)
-        if (!(times[i] > times[i - 1])) return AZ_ERR_VALUE; // (the Hermite interval needs a length > 0; NaN fails too)
-    if (c->n == 0) return AZ_OK;
+    for (size_t i = 1; i < n; ++i)
+        if (!(times[i] > times[i - 1])) return false;
+    return true;
+}
+
+// azh_find_passes_*: propagate to `mode` with rates, satellite-major, into the handle's scratch one row window at a time (at most
+// kPassScratch bytes: pos + vel + err), and scan every window's rows [lo, hi) with scan(lo, hi) behind its propagation.  With no
+// grid point the n_cnt counts are zeroed.
+static constexpr size_t kPassScratch = size_t(512) << 20;
+extern "C++" { // (templates)
+template <class Scan>
+static int32_t pass_windows(azh_constellation *c, const double *times, size_t n_times, const double *offsets, double reference_jd,
+                            int32_t mode, uint32_t *d_n, size_t n_cnt, hipStream_t st, Scan &&scan)
+{
     if (n_times == 0) {
-        HIP_TRY(hipMemsetAsync(d_n, 0, sizeof(uint32_t) * c->n, st));
+        HIP_TRY(hipMemsetAsync(d_n, 0, sizeof(uint32_t) * n_cnt, st));
         return AZ_OK;
     }
-    if (int32_t rc = stage_inputs(c, times, n_times, offsets, nullptr, AZ_OUT_TOPOCENTRIC, reference_jd, st); rc != AZ_OK) return rc;
+    if (int32_t rc = stage_inputs(c, times, n_times, offsets, nullptr, mode, reference_jd, st); rc != AZ_OK) return rc;
     const size_t per_row = n_times * (6 * sizeof(double) + 1);
     const size_t rows_w = std::max<size_t>(1, std::min(c->n, kPassScratch / per_row));
     const size_t words = rows_w * n_times * 3;
@@ -2564,6 +2571,37 @@ static int32_t find_passes(azh_constellation *c, const double *times, size_t n_t
                                     reinterpret_cast<uint8_t *>(eb), st, 0, lo, hi);
             rc != AZ_OK)
             return rc;
+        if (int32_t rc = scan(lo, hi); rc != AZ_OK) return rc;
+    }
+    return AZ_OK;
+}
+
+// the _host variants: run(d_out, d_n) on the handle's stream into its grow-only buffers of n_rec records and n_cnt counts, and
+// copy both back (the first failure wins; the final sync always runs)
+template <class Run>
+static int32_t passes_to_host(azh_constellation *c, size_t n_rec, size_t n_cnt, azh_pass *out, uint32_t *n_passes, Run &&run)
+{
+    if (c->d_pass_out.cap < n_rec || c->d_pass_n.cap < n_cnt) HIP_TRY(hipStreamSynchronize(c->s_main));
+    if ((n_rec && c->d_pass_out.ensure(n_rec) != AZ_OK) || c->d_pass_n.ensure(n_cnt) != AZ_OK) return AZ_ERR_HIP;
+    int32_t rc = run(n_rec ? c->d_pass_out.p : nullptr, c->d_pass_n.p);
+    if (rc == AZ_OK && !hip_ok(hipMemcpyAsync(n_passes, c->d_pass_n.p, sizeof(uint32_t) * n_cnt, hipMemcpyDeviceToHost, c->s_main), "D2H"))
+        rc = AZ_ERR_HIP;
+    if (rc == AZ_OK && n_rec &&
+        !hip_ok(hipMemcpyAsync(out, c->d_pass_out.p, sizeof(azh_pass) * n_rec, hipMemcpyDeviceToHost, c->s_main), "D2H"))
+        rc = AZ_ERR_HIP;
+    if (!hip_ok(hipStreamSynchronize(c->s_main), "sync") && rc == AZ_OK) rc = AZ_ERR_HIP;
+    return rc;
+}
+} // extern "C++"
+
+// one observer: topocentric look angles, scanned by k_passes
+static int32_t find_passes(azh_constellation *c, const double *times, size_t n_times, const double *offsets, double reference_jd,
+                           double min_elevation_deg, azh_pass *d_out, size_t max_passes, uint32_t *d_n, hipStream_t st)
+{
+    if (!c->have_observer || !std::isfinite(min_elevation_deg) || max_passes > 0xffffffffu || !times_increasing(times, n_times))
+        return AZ_ERR_VALUE;
+    if (c->n == 0) return AZ_OK;
+    return pass_windows(c, times, n_times, offsets, reference_jd, AZ_OUT_TOPOCENTRIC, d_n, c->n, st, [&](size_t lo, size_t hi) -> int32_t {
         PassArgs q{};
         q.pos = c->d_pass_pos.p; q.vel = c->d_pass_vel.p; q.err = c->d_pass_err.p;
         q.times = c->d_times.p; q.n_times = (unsigned)n_times;
@@ -2572,8 +2610,8 @@ static int32_t find_passes(azh_constellation *c, const double *times, size_t n_t
         q.out = d_out; q.max_passes = (unsigned)max_passes; q.n_passes = d_n;
         hipLaunchKernelGGL(k_passes, dim3((unsigned)((hi - lo + AZ_PASS_WAVES - 1) / AZ_PASS_WAVES)), dim3(64 * AZ_PASS_WAVES), 0, st, q);
         HIP_TRY(hipGetLastError());
-    }
-    return AZ_OK;
+        return AZ_OK;
+    });
 }
 
 int32_t azh_find_passes_device(azh_constellation *c, const double *times, size_t n_times, const double *offsets, double reference_jd,
@@ -2594,24 +2632,14 @@ int32_t azh_find_passes_host(azh_constellation *c, const double *times, size_t n
         if (!c || !n_passes || (n_times && !times) || (max_passes && !out)) return AZ_ERR_NULL_POINTER;
         if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
         if (c->n == 0) return find_passes(c, times, n_times, offsets, reference_jd, min_elevation_deg, nullptr, max_passes, nullptr, c->s_main);
-        const size_t n_rec = c->n * max_passes;
-        if (c->d_pass_out.cap < n_rec || c->d_pass_n.cap < c->n) HIP_TRY(hipStreamSynchronize(c->s_main));
-        if ((n_rec && c->d_pass_out.ensure(n_rec) != AZ_OK) || c->d_pass_n.ensure(c->n) != AZ_OK) return AZ_ERR_HIP;
-        int32_t rc = find_passes(c, times, n_times, offsets, reference_jd, min_elevation_deg, n_rec ? c->d_pass_out.p : nullptr, max_passes,
-                                 c->d_pass_n.p, c->s_main);
-        if (rc == AZ_OK && !hip_ok(hipMemcpyAsync(n_passes, c->d_pass_n.p, sizeof(uint32_t) * c->n, hipMemcpyDeviceToHost, c->s_main), "D2H"))
-            rc = AZ_ERR_HIP;
-        if (rc == AZ_OK && n_rec &&
-            !hip_ok(hipMemcpyAsync(out, c->d_pass_out.p, sizeof(azh_pass) * n_rec, hipMemcpyDeviceToHost, c->s_main), "D2H"))
-            rc = AZ_ERR_HIP;
-        if (!hip_ok(hipStreamSynchronize(c->s_main), "sync") && rc == AZ_OK) rc = AZ_ERR_HIP;
-        return rc;
+        return passes_to_host(c, c->n * max_passes, c->n, out, n_passes, [&](azh_pass *d_out, uint32_t *d_n) {
+            return find_passes(c, times, n_times, offsets, reference_jd, min_elevation_deg, d_out, max_passes, d_n, c->s_main);
+        });
     });
 }
 
-// azh_find_passes_stations_*: propagate to AZ_OUT_ECEF with velocities, satellite-major, into the same scratch one row window
-// at a time, and scan every window's rows with k_passes_stations once per group of AZ_STATION_GROUP stations: the propagation
-// does not depend on the station, and a group reads the scratch once.
+// azh_find_passes_stations_*: Earth-fixed states with velocities in the same scratch, scanned by k_passes_stations once per group
+// of AZ_STATION_GROUP stations: the propagation does not depend on the station, and a group reads the scratch once.
 static int32_t find_passes_stations(azh_constellation *c, const double *times, size_t n_times, const double *offsets,
                                     double reference_jd, const double *lla, const double *mask_deg, size_t n_st, azh_pass *d_out,
                                     size_t max_passes, uint32_t *d_n, hipStream_t st)
@@ -2627,28 +2655,7 @@ static int32_t find_passes_stations(azh_constellation *c, const double *times, s
         S.s2 = std::sin(S.min_el) * std::fabs(std::sin(S.min_el));
     }
     HIP_TRY(hipMemcpyAsync(c->d_stations.p, c->h_stations.data(), sizeof(AzStation) * n_st, hipMemcpyHostToDevice, st));
-    if (n_times == 0) {
-        HIP_TRY(hipMemsetAsync(d_n, 0, sizeof(uint32_t) * c->n * n_st, st));
-        return AZ_OK;
-    }
-    if (int32_t rc = stage_inputs(c, times, n_times, offsets, nullptr, AZ_OUT_ECEF, reference_jd, st); rc != AZ_OK) return rc;
-    const size_t per_row = n_times * (6 * sizeof(double) + 1);
-    const size_t rows_w = std::max<size_t>(1, std::min(c->n, kPassScratch / per_row));
-    const size_t words = rows_w * n_times * 3;
-    if (c->d_pass_pos.cap < words || c->d_pass_vel.cap < words || c->d_pass_err.cap < rows_w * n_times)
-        HIP_TRY(hipStreamSynchronize(st)); // (launches in flight use the old buffers)
-    if (c->d_pass_pos.ensure(words) != AZ_OK || c->d_pass_vel.ensure(words) != AZ_OK || c->d_pass_err.ensure(rows_w * n_times) != AZ_OK)
-        return AZ_ERR_HIP;
-    for (size_t lo = 0; lo < c->n; lo += rows_w) {
-        const size_t hi = std::min(c->n, lo + rows_w);
-        const size_t shift = lo * n_times; // (the window's rows land at the start of the scratch, as in find_passes)
-        const uintptr_t pb = reinterpret_cast<uintptr_t>(c->d_pass_pos.p) - 3 * shift * sizeof(double);
-        const uintptr_t vb = reinterpret_cast<uintptr_t>(c->d_pass_vel.p) - 3 * shift * sizeof(double);
-        const uintptr_t eb = reinterpret_cast<uintptr_t>(c->d_pass_err.p) - shift;
-        if (int32_t rc = launch_all(c, reinterpret_cast<double *>(pb), reinterpret_cast<double *>(vb), AZ_LAYOUT_SAT_MAJOR, 0,
-                                    reinterpret_cast<uint8_t *>(eb), st, 0, lo, hi);
-            rc != AZ_OK)
-            return rc;
+    return pass_windows(c, times, n_times, offsets, reference_jd, AZ_OUT_ECEF, d_n, c->n * n_st, st, [&](size_t lo, size_t hi) -> int32_t {
         for (size_t g = 0; g < n_st; g += AZ_STATION_GROUP) {
             StationPassArgs q{};
             q.pos = c->d_pass_pos.p; q.vel = c->d_pass_vel.p; q.err = c->d_pass_err.p;
@@ -2660,8 +2667,8 @@ static int32_t find_passes_stations(azh_constellation *c, const double *times, s
                                0, st, q);
             HIP_TRY(hipGetLastError());
         }
-    }
-    return AZ_OK;
+        return AZ_OK;
+    });
 }
 
 // the argument rules of both variants, checked before the device is touched; n_rec = the records out holds
@@ -2675,9 +2682,7 @@ static int32_t stations_args(const azh_constellation *c, const double *times, si
         return AZ_ERR_VALUE;
     for (size_t k = 0; k < n_st; ++k)
         if (!observer_ok(lla[3 * k], lla[3 * k + 1], lla[3 * k + 2]) || !std::isfinite(mask_deg[k])) return AZ_ERR_VALUE;
-    for (size_t i = 1; i < n_times; ++i)
-        if (!(times[i] > times[i - 1])) return AZ_ERR_VALUE; // (the Hermite interval needs a length > 0; NaN fails too)
-    return AZ_OK;
+    return times_increasing(times, n_times) ? AZ_OK : AZ_ERR_VALUE;
 }
 
 int32_t azh_find_passes_stations_device(azh_constellation *c, const double *times, size_t n_times, const double *offsets,
@@ -2709,18 +2714,10 @@ int32_t azh_find_passes_stations_host(azh_constellation *c, const double *times,
             return rc;
         if (n_stations == 0 || c->n == 0) return AZ_OK;
         if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
-        const size_t n_cnt = c->n * n_stations;
-        if (c->d_pass_out.cap < n_rec || c->d_pass_n.cap < n_cnt) HIP_TRY(hipStreamSynchronize(c->s_main));
-        if ((n_rec && c->d_pass_out.ensure(n_rec) != AZ_OK) || c->d_pass_n.ensure(n_cnt) != AZ_OK) return AZ_ERR_HIP;
-        int32_t rc = find_passes_stations(c, times, n_times, offsets, reference_jd, stations_lla, min_elevation_deg, n_stations,
-                                          n_rec ? c->d_pass_out.p : nullptr, max_passes, c->d_pass_n.p, c->s_main);
-        if (rc == AZ_OK && !hip_ok(hipMemcpyAsync(n_passes, c->d_pass_n.p, sizeof(uint32_t) * n_cnt, hipMemcpyDeviceToHost, c->s_main), "D2H"))
-            rc = AZ_ERR_HIP;
-        if (rc == AZ_OK && n_rec &&
-            !hip_ok(hipMemcpyAsync(out, c->d_pass_out.p, sizeof(azh_pass) * n_rec, hipMemcpyDeviceToHost, c->s_main), "D2H"))
-            rc = AZ_ERR_HIP;
-        if (!hip_ok(hipStreamSynchronize(c->s_main), "sync") && rc == AZ_OK) rc = AZ_ERR_HIP;
-        return rc;
+        return passes_to_host(c, n_rec, c->n * n_stations, out, n_passes, [&](azh_pass *d_out, uint32_t *d_n) {
+            return find_passes_stations(c, times, n_times, offsets, reference_jd, stations_lla, min_elevation_deg, n_stations, d_out,
+                                        max_passes, d_n, c->s_main);
+        });
     });
 }
 

@@ -142,6 +142,174 @@ __device__ __forceinline__ double az_wave_max(double x)
     return x;
 }
 
+// ---- the pass tracker both kernels share ---------------------------------------------------------------------------------
+// The kernels differ only in where a grid point's look angles come from -- a look functor: look(i, a, ad) fills (az, el, range)
+// and their rates at grid point i -- and in where a station's pass state waits between chunks.  The rest is this.
+struct AzLookScratch { // the topocentric scratch as it stands
+    const double *P, *V;
+    __device__ __forceinline__ void operator()(size_t i, double a[3], double ad[3]) const
+    {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            a[k] = P[3 * i + k];
+            ad[k] = V[3 * i + k];
+        }
+    }
+};
+struct AzLookStation { // az_topocentric<true> of the ECEF state of the scratch, from observer o
+    AzLookScratch state;
+    const AzObserver &o;
+    __device__ __forceinline__ void operator()(size_t i, double a[3], double ad[3]) const
+    {
+        state(i, a, ad);
+        az_topocentric<true>(a, ad, o);
+    }
+};
+
+// one station's pass under way, and what it has stored
+struct AzPassState {
+    azh_pass cur;
+    double best_el;
+    unsigned best_i, count;
+};
+// one row's constants, for one station
+struct AzPassRow {
+    const unsigned char *E; // the row's error codes
+    const double *T;        // the time axis
+    azh_pass *out;          // the station's records of the row: max_passes of them
+    double min_el;          // rad
+    unsigned n, max_passes, lane;
+};
+__device__ __forceinline__ unsigned az_readlane_u32(unsigned x, unsigned l) { return (unsigned)__builtin_amdgcn_readlane((int)x, (int)l); }
+
+// the record of a pass whose set is known: culmination refinement, store (the first max_passes only)
+template <class Look>
+__device__ __forceinline__ void az_pass_finish(const AzPassRow &r, const Look &look, AzPassState &u)
+{
+    double t_c = r.T[u.best_i], e_c = u.best_el;
+    const unsigned k = u.best_i;
+#pragma unroll
+    for (int side = 0; side < 2; ++side) {
+        if (side == 0 && k == 0) continue;
+        if (side == 1 && k + 1 >= r.n) continue;
+        const unsigned i0 = side == 0 ? k - 1 : k, i1 = i0 + 1;
+        if (r.E[i0] != 0 || r.E[i1] != 0) continue;
+        double a0[3], d0[3], a1[3], d1[3];
+        look(i0, a0, d0);
+        look(i1, a1, d1);
+        if (!(d0[1] > 0.0 && d1[1] < 0.0)) continue;
+        const double dt = r.T[i1] - r.T[i0];
+        double s;
+        const double e = az_culmination(a0, d0, a1, d1, dt, s);
+        if (e > e_c) {
+            e_c = e;
+            t_c = fma(s, dt, r.T[i0]);
+        }
+    }
+    u.cur.t_culm_min = t_c;
+    u.cur.max_elevation_rad = e_c;
+    u.cur.grid_culm = k;
+    if (r.lane == 0 && u.count < r.max_passes) r.out[u.count] = u.cur;
+    ++u.count;
+}
+
+// one chunk of 64 grid points from base: this lane's elevation el (read only on live lanes) and failure bad, the ballots of up,
+// failed (with the point before base in bit 0) and live points.  in_pass (the pass under way, wave-uniform) is the up state of
+// the point before base.
+template <class Look>
+__device__ __forceinline__ void az_pass_chunk(const AzPassRow &r, const Look &look, unsigned base, double el, bool bad, uint64_t m,
+                                              uint64_t prevb, uint64_t ml, AzPassState &u, bool &in_pass)
+{
+    const unsigned lane = r.lane, i = base + lane;
+    const bool live = i < r.n;
+    const uint64_t prev = (m << 1) | (uint64_t)in_pass;
+    const uint64_t rises = m & ~prev, sets = ~m & prev & ml;
+    const bool is_rise = (rises >> lane) & 1u, is_set = (sets >> lane) & 1u;
+    // refinement by the lane that owns the event: time, azimuth and flag of a rise (interval [i-1, i], i first up point)
+    // or a set (interval [i-1, i], i-1 last up point)
+    double ev_t = 0.0, ev_az = 0.0;
+    unsigned ev_fl = 0;
+    if (is_rise || is_set) {
+        const bool prev_bad = (prevb >> lane) & 1u;
+        if (is_rise && i == 0) {
+            double a[3], ad[3];
+            look(0, a, ad);
+            ev_t = r.T[0];
+            ev_az = a[0];
+            ev_fl = AZH_PASS_UP_AT_START;
+        } else if ((is_rise && prev_bad) || (is_set && bad)) {
+            const unsigned j = is_rise ? i : i - 1; // the open end stays on the grid point that propagated
+            double a[3], ad[3];
+            look(j, a, ad);
+            ev_t = r.T[j];
+            ev_az = a[0];
+            ev_fl = AZH_PASS_CUT_BY_ERROR;
+        } else {
+            const unsigned i0 = i - 1;
+            double a0[3], d0[3], a1[3], d1[3];
+            look(i0, a0, d0);
+            look(i, a1, d1);
+            const double dt = r.T[i] - r.T[i0];
+            const double f0 = a0[1] - r.min_el, f1 = a1[1] - r.min_el;
+            const double s = az_herm_root(f0, f1, 60.0 * dt * d0[1], 60.0 * dt * d1[1]);
+            ev_t = fma(s, dt, r.T[i0]);
+            ev_az = az_herm_azimuth(a0[0], a1[0], 60.0 * dt * d0[0], 60.0 * dt * d1[0], s);
+        }
+    }
+    // the segment [lo, hi) of this chunk belongs to the pass under way: its grid maximum (earliest index on ties)
+    auto seg_max = [&](unsigned lo, unsigned hi) {
+        const bool in = lane >= lo && lane < hi && live;
+        const double mx = az_wave_max(in ? el : -1.0e300);
+        const uint64_t hit = __ballot(in && el == mx);
+        if (hit && mx > u.best_el) {
+            u.best_el = mx;
+            u.best_i = base + (unsigned)__builtin_ctzll(hit);
+        }
+    };
+    // the events in lane order: a rise opens a record, a set closes it
+    uint64_t ev = rises | sets;
+    unsigned seg_lo = 0;
+    while (ev) {
+        const unsigned L = (unsigned)__builtin_ctzll(ev);
+        ev &= ev - 1u;
+        if (in_pass && L > seg_lo) seg_max(seg_lo, L);
+        const double t_e = az_readlane_f64(ev_t, L), az_e = az_readlane_f64(ev_az, L);
+        const unsigned fl_e = az_readlane_u32(ev_fl, L);
+        if ((rises >> L) & 1u) {
+            in_pass = true;
+            u.cur = azh_pass{};
+            u.cur.t_rise_min = t_e;
+            u.cur.rise_azimuth_rad = az_e;
+            u.cur.flags = fl_e;
+            u.cur.grid_rise = base + L;
+            u.best_el = -1.0e300;
+            u.best_i = base + L;
+        } else {
+            u.cur.t_set_min = t_e;
+            u.cur.set_azimuth_rad = az_e;
+            u.cur.flags |= fl_e;
+            u.cur.grid_set = base + L - 1u;
+            az_pass_finish(r, look, u);
+            in_pass = false;
+        }
+        seg_lo = L;
+    }
+    if (in_pass) seg_max(seg_lo, 64u);
+}
+
+// a pass still up at the last grid point
+template <class Look>
+__device__ __forceinline__ void az_pass_close_at_end(const AzPassRow &r, const Look &look, AzPassState &u)
+{
+    double a[3], ad[3];
+    look(r.n - 1, a, ad);
+    u.cur.t_set_min = r.T[r.n - 1];
+    u.cur.set_azimuth_rad = a[0];
+    u.cur.flags |= AZH_PASS_UP_AT_END;
+    u.cur.grid_set = r.n - 1;
+    az_pass_finish(r, look, u);
+}
+
 #define AZ_PASS_WAVES 4
 __global__ void __launch_bounds__(64 * AZ_PASS_WAVES) k_passes(PassArgs p)
 {
@@ -149,132 +317,28 @@ __global__ void __launch_bounds__(64 * AZ_PASS_WAVES) k_passes(PassArgs p)
     const unsigned wrow = blockIdx.x * AZ_PASS_WAVES + (threadIdx.x >> 6);
     if (wrow >= p.n_rows) return; // (wave-uniform)
     const unsigned n = p.n_times;
-    const double *P = p.pos + (size_t)wrow * n * 3, *V = p.vel + (size_t)wrow * n * 3;
-    const unsigned char *E = p.err + (size_t)wrow * n;
-    const double *T = p.times;
     const size_t srow = (size_t)p.row0 + wrow;
-    azh_pass *out = p.out + srow * p.max_passes;
-    const double min_el = p.min_el;
+    const double *P = p.pos + (size_t)wrow * n * 3;
+    const unsigned char *E = p.err + (size_t)wrow * n;
+    const AzLookScratch look{P, p.vel + (size_t)wrow * n * 3};
+    const AzPassRow r{E, p.times, p.out + srow * p.max_passes, p.min_el, n, p.max_passes, lane};
 
-    // the pass under way (wave-uniform)
+    AzPassState u{}; // the pass under way (wave-uniform)
+    u.best_el = -1.0e300;
     bool in_pass = false;
-    unsigned count = 0;
-    azh_pass cur{};
-    double best_el = -1.0e300;
-    unsigned best_i = 0;
-    uint64_t carry_up = 0, carry_bad = 0; // state of the grid point before this iteration's first
-
-    // the record of a pass whose set is known: culmination refinement, store (the first max_passes only)
-    auto finish = [&]() {
-        double t_c = T[best_i], e_c = best_el;
-        const unsigned k = best_i;
-#pragma unroll
-        for (int side = 0; side < 2; ++side) {
-            if (side == 0 && k == 0) continue;
-            if (side == 1 && k + 1 >= n) continue;
-            const unsigned i0 = side == 0 ? k - 1 : k, i1 = i0 + 1;
-            if (E[i0] != 0 || E[i1] != 0) continue;
-            const double d0 = V[3 * (size_t)i0 + 1], d1 = V[3 * (size_t)i1 + 1];
-            if (!(d0 > 0.0 && d1 < 0.0)) continue;
-            const double dt = T[i1] - T[i0];
-            double s;
-            const double e = az_culmination(P + 3 * (size_t)i0, V + 3 * (size_t)i0, P + 3 * (size_t)i1, V + 3 * (size_t)i1, dt, s);
-            if (e > e_c) {
-                e_c = e;
-                t_c = fma(s, dt, T[i0]);
-            }
-        }
-        cur.t_culm_min = t_c;
-        cur.max_elevation_rad = e_c;
-        cur.grid_culm = k;
-        if (lane == 0 && count < p.max_passes) out[count] = cur;
-        ++count;
-    };
-
+    uint64_t carry_bad = 0; // the grid point before this iteration's first failed
     for (unsigned base = 0; base < n; base += 64) {
         const unsigned i = base + lane;
         const bool live = i < n;
         const double el = live ? P[3 * (size_t)i + 1] : 0.0;
         const bool bad = live && E[i] != 0;
-        const bool up = live && !bad && el >= min_el;
+        const bool up = live && !bad && el >= r.min_el;
         const uint64_t m = __ballot(up), mb = __ballot(bad), ml = __ballot(live);
-        const uint64_t prev = (m << 1) | carry_up, prevb = (mb << 1) | carry_bad;
-        const uint64_t rises = m & ~prev, sets = ~m & prev & ml;
-        const bool is_rise = (rises >> lane) & 1u, is_set = (sets >> lane) & 1u;
-        // refinement by the lane that owns the event: time, azimuth and flag of a rise (interval [i-1, i], i first up point)
-        // or a set (interval [i-1, i], i-1 last up point)
-        double ev_t = 0.0, ev_az = 0.0;
-        unsigned ev_fl = 0;
-        if (is_rise || is_set) {
-            const bool prev_bad = (prevb >> lane) & 1u;
-            if (is_rise && i == 0) {
-                ev_t = T[0];
-                ev_az = P[0];
-                ev_fl = AZH_PASS_UP_AT_START;
-            } else if ((is_rise && prev_bad) || (is_set && bad)) {
-                const unsigned j = is_rise ? i : i - 1; // the open end stays on the grid point that propagated
-                ev_t = T[j];
-                ev_az = P[3 * (size_t)j];
-                ev_fl = AZH_PASS_CUT_BY_ERROR;
-            } else {
-                const unsigned i0 = i - 1;
-                const double dt = T[i] - T[i0];
-                const double f0 = P[3 * (size_t)i0 + 1] - min_el, f1 = el - min_el;
-                const double s = az_herm_root(f0, f1, 60.0 * dt * V[3 * (size_t)i0 + 1], 60.0 * dt * V[3 * (size_t)i + 1]);
-                ev_t = fma(s, dt, T[i0]);
-                ev_az = az_herm_azimuth(P[3 * (size_t)i0], P[3 * (size_t)i], 60.0 * dt * V[3 * (size_t)i0], 60.0 * dt * V[3 * (size_t)i], s);
-            }
-        }
-        // the segment [lo, hi) of this iteration belongs to the pass under way: its grid maximum (earliest index on ties)
-        auto seg_max = [&](unsigned lo, unsigned hi) {
-            const bool in = lane >= lo && lane < hi && live;
-            const double mx = az_wave_max(in ? el : -1.0e300);
-            const uint64_t hit = __ballot(in && el == mx);
-            if (hit && mx > best_el) {
-                best_el = mx;
-                best_i = base + (unsigned)__builtin_ctzll(hit);
-            }
-        };
-        uint64_t ev = rises | sets;
-        unsigned seg_lo = 0;
-        while (ev) {
-            const unsigned L = (unsigned)__builtin_ctzll(ev);
-            ev &= ev - 1u;
-            if (in_pass && L > seg_lo) seg_max(seg_lo, L);
-            const double t_e = az_readlane_f64(ev_t, L), az_e = az_readlane_f64(ev_az, L);
-            const unsigned fl_e = (unsigned)__builtin_amdgcn_readlane((int)ev_fl, (int)L);
-            if ((rises >> L) & 1u) {
-                in_pass = true;
-                cur = azh_pass{};
-                cur.t_rise_min = t_e;
-                cur.rise_azimuth_rad = az_e;
-                cur.flags = fl_e;
-                cur.grid_rise = base + L;
-                best_el = -1.0e300;
-                best_i = base + L;
-            } else {
-                cur.t_set_min = t_e;
-                cur.set_azimuth_rad = az_e;
-                cur.flags |= fl_e;
-                cur.grid_set = base + L - 1u;
-                finish();
-                in_pass = false;
-            }
-            seg_lo = L;
-        }
-        if (in_pass) seg_max(seg_lo, 64u);
-        carry_up = m >> 63;
+        az_pass_chunk(r, look, base, el, bad, m, (mb << 1) | carry_bad, ml, u, in_pass);
         carry_bad = mb >> 63;
     }
-    if (in_pass) {
-        // still up at the last grid point
-        cur.t_set_min = T[n - 1];
-        cur.set_azimuth_rad = P[3 * (size_t)(n - 1)];
-        cur.flags |= AZH_PASS_UP_AT_END;
-        cur.grid_set = n - 1;
-        finish();
-    }
-    if (lane == 0) p.n_passes[srow] = count;
+    if (in_pass) az_pass_close_at_end(r, look, u);
+    if (lane == 0) p.n_passes[srow] = u.count;
 }
 
 // ---- several stations per call (azh_find_passes_stations_*) -------------------------------------------------------------
@@ -309,24 +373,7 @@ struct StationPassArgs {
     uint32_t *n_passes; // [n_stations][n_sats]
 };
 
-// look angles and their rates of grid point i from observer o
-__device__ __forceinline__ void az_look(const double *P, const double *V, size_t i, const AzObserver &o, double a[3], double ad[3])
-{
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        a[k] = P[3 * i + k];
-        ad[k] = V[3 * i + k];
-    }
-    az_topocentric<true>(a, ad, o);
-}
-
-// one station's pass under way, and what it has stored
-struct AzPassState {
-    azh_pass cur;
-    double best_el;
-    unsigned best_i, count;
-};
-__device__ __forceinline__ unsigned az_readlane_u32(unsigned x, unsigned l) { return (unsigned)__builtin_amdgcn_readlane((int)x, (int)l); }
+// station l's pass state, from lane l into wave-uniform registers
 __device__ __forceinline__ AzPassState az_state_of(const AzPassState &s, unsigned l)
 {
     AzPassState u;
@@ -352,54 +399,27 @@ __global__ void __launch_bounds__(64 * AZ_PASS_WAVES) k_passes_stations(StationP
     const unsigned wrow = blockIdx.x * AZ_PASS_WAVES + (threadIdx.x >> 6);
     if (wrow >= p.n_rows) return; // (wave-uniform)
     const unsigned n = p.n_times;
+    const size_t srow = (size_t)p.row0 + wrow;
     const double *P = p.pos + (size_t)wrow * n * 3, *V = p.vel + (size_t)wrow * n * 3;
     const unsigned char *E = p.err + (size_t)wrow * n;
-    const double *T = p.times;
-    const size_t srow = (size_t)p.row0 + wrow;
+    auto row = [&](unsigned j, const AzStation &S) { // station j's records of the row, and mask
+        return AzPassRow{E, p.times, p.out + ((size_t)(p.st0 + j) * p.n_sats + srow) * p.max_passes, S.min_el, n, p.max_passes, lane};
+    };
 
     AzPassState mine{};      // station `lane`'s
     mine.best_el = -1.0e300;
     uint64_t in_pass_mask = 0; // bit j: station j has a pass under way (its last grid point was up)
     uint64_t carry_bad = 0;    // the grid point before this iteration's first failed
 
-    // the record of a pass whose set is known: culmination refinement, store (the first max_passes only)
-    auto finish = [&](const AzStation &S, AzPassState &u, unsigned j) {
-        double t_c = T[u.best_i], e_c = u.best_el;
-        const unsigned k = u.best_i;
-#pragma unroll
-        for (int side = 0; side < 2; ++side) {
-            if (side == 0 && k == 0) continue;
-            if (side == 1 && k + 1 >= n) continue;
-            const unsigned i0 = side == 0 ? k - 1 : k, i1 = i0 + 1;
-            if (E[i0] != 0 || E[i1] != 0) continue;
-            double a0[3], d0[3], a1[3], d1[3];
-            az_look(P, V, i0, S.o, a0, d0);
-            az_look(P, V, i1, S.o, a1, d1);
-            if (!(d0[1] > 0.0 && d1[1] < 0.0)) continue;
-            const double dt = T[i1] - T[i0];
-            double s;
-            const double e = az_culmination(a0, d0, a1, d1, dt, s);
-            if (e > e_c) {
-                e_c = e;
-                t_c = fma(s, dt, T[i0]);
-            }
-        }
-        u.cur.t_culm_min = t_c;
-        u.cur.max_elevation_rad = e_c;
-        u.cur.grid_culm = k;
-        if (lane == 0 && u.count < p.max_passes) p.out[((size_t)(p.st0 + j) * p.n_sats + srow) * p.max_passes + u.count] = u.cur;
-        ++u.count;
-    };
-
     for (unsigned base = 0; base < n; base += 64) {
         const unsigned i = base + lane;
         const bool live = i < n;
-        double r[3] = {0.0, 0.0, 0.0};
+        double R[3] = {0.0, 0.0, 0.0};
         bool bad = false;
         if (live) {
-            r[0] = P[3 * (size_t)i];
-            r[1] = P[3 * (size_t)i + 1];
-            r[2] = P[3 * (size_t)i + 2];
+            R[0] = P[3 * (size_t)i];
+            R[1] = P[3 * (size_t)i + 1];
+            R[2] = P[3 * (size_t)i + 2];
             bad = E[i] != 0;
         }
         const bool ok = live && !bad;
@@ -407,114 +427,35 @@ __global__ void __launch_bounds__(64 * AZ_PASS_WAVES) k_passes_stations(StationP
         const uint64_t prevb = (mb << 1) | carry_bad;
         for (unsigned j = 0; j < p.n_st; ++j) {
             const AzStation S = p.st[j]; // (wave-uniform)
-            const bool was_in = (in_pass_mask >> j) & 1u;
+            bool in_pass = (in_pass_mask >> j) & 1u;
             // the cheap test: U |U| against s |s| |rho|^2, exact elevation near the mask
-            const double dx = r[0] - S.o.x, dy = r[1] - S.o.y, dz = r[2] - S.o.z;
+            const double dx = R[0] - S.o.x, dy = R[1] - S.o.y, dz = R[2] - S.o.z;
             const double q = fma(S.o.cos_lon, dx, S.o.sin_lon * dy);
             const double U = fma(S.o.cos_lat, q, S.o.sin_lat * dz);
             const double rho2 = fma(dx, dx, fma(dy, dy, dz * dz));
             const double d = fma(U, fabs(U), -(S.s2 * rho2)), margin = 1.0e-12 * rho2;
-            if (!was_in && !az_any(ok && d >= -margin)) continue; // nothing up, nothing under way
+            if (!in_pass && !az_any(ok && d >= -margin)) continue; // nothing up, nothing under way
             double el = 0.0;
             if (ok) {
-                double a[3] = {r[0], r[1], r[2]}, ad[3] = {0.0, 0.0, 0.0}; // (the position slot does not read the velocity)
+                double a[3] = {R[0], R[1], R[2]}, ad[3] = {0.0, 0.0, 0.0}; // (the position slot does not read the velocity)
                 az_topocentric<true>(a, ad, S.o);
                 el = a[1];
             }
-            const bool up = ok && el >= S.min_el;
-            const uint64_t m = __ballot(up);
-            if (!was_in && m == 0) continue;
+            const uint64_t m = __ballot(ok && el >= S.min_el);
+            if (!in_pass && m == 0) continue;
 
             AzPassState u = az_state_of(mine, j);
-            bool in_pass = was_in;
-            const uint64_t prev = (m << 1) | (uint64_t)was_in;
-            const uint64_t rises = m & ~prev, sets = ~m & prev & ml;
-            const bool is_rise = (rises >> lane) & 1u, is_set = (sets >> lane) & 1u;
-            // refinement by the lane that owns the event, as k_passes
-            double ev_t = 0.0, ev_az = 0.0;
-            unsigned ev_fl = 0;
-            if (is_rise || is_set) {
-                const bool prev_bad = (prevb >> lane) & 1u;
-                if (is_rise && i == 0) {
-                    double a[3], ad[3];
-                    az_look(P, V, 0, S.o, a, ad);
-                    ev_t = T[0];
-                    ev_az = a[0];
-                    ev_fl = AZH_PASS_UP_AT_START;
-                } else if ((is_rise && prev_bad) || (is_set && bad)) {
-                    const unsigned jj = is_rise ? i : i - 1; // the open end stays on the grid point that propagated
-                    double a[3], ad[3];
-                    az_look(P, V, jj, S.o, a, ad);
-                    ev_t = T[jj];
-                    ev_az = a[0];
-                    ev_fl = AZH_PASS_CUT_BY_ERROR;
-                } else {
-                    const unsigned i0 = i - 1;
-                    double a0[3], d0[3], a1[3], d1[3];
-                    az_look(P, V, i0, S.o, a0, d0);
-                    az_look(P, V, i, S.o, a1, d1);
-                    const double dt = T[i] - T[i0];
-                    const double f0 = a0[1] - S.min_el, f1 = a1[1] - S.min_el;
-                    const double s = az_herm_root(f0, f1, 60.0 * dt * d0[1], 60.0 * dt * d1[1]);
-                    ev_t = fma(s, dt, T[i0]);
-                    ev_az = az_herm_azimuth(a0[0], a1[0], 60.0 * dt * d0[0], 60.0 * dt * d1[0], s);
-                }
-            }
-            // the segment [lo, hi) of this iteration belongs to the pass under way: its grid maximum (earliest index on ties)
-            auto seg_max = [&](unsigned lo, unsigned hi) {
-                const bool in = lane >= lo && lane < hi && live;
-                const double mx = az_wave_max(in ? el : -1.0e300);
-                const uint64_t hit = __ballot(in && el == mx);
-                if (hit && mx > u.best_el) {
-                    u.best_el = mx;
-                    u.best_i = base + (unsigned)__builtin_ctzll(hit);
-                }
-            };
-            uint64_t ev = rises | sets;
-            unsigned seg_lo = 0;
-            while (ev) {
-                const unsigned L = (unsigned)__builtin_ctzll(ev);
-                ev &= ev - 1u;
-                if (in_pass && L > seg_lo) seg_max(seg_lo, L);
-                const double t_e = az_readlane_f64(ev_t, L), az_e = az_readlane_f64(ev_az, L);
-                const unsigned fl_e = az_readlane_u32(ev_fl, L);
-                if ((rises >> L) & 1u) {
-                    in_pass = true;
-                    u.cur = azh_pass{};
-                    u.cur.t_rise_min = t_e;
-                    u.cur.rise_azimuth_rad = az_e;
-                    u.cur.flags = fl_e;
-                    u.cur.grid_rise = base + L;
-                    u.best_el = -1.0e300;
-                    u.best_i = base + L;
-                } else {
-                    u.cur.t_set_min = t_e;
-                    u.cur.set_azimuth_rad = az_e;
-                    u.cur.flags |= fl_e;
-                    u.cur.grid_set = base + L - 1u;
-                    finish(S, u, j);
-                    in_pass = false;
-                }
-                seg_lo = L;
-            }
-            if (in_pass) seg_max(seg_lo, 64u);
+            az_pass_chunk(row(j, S), AzLookStation{{P, V}, S.o}, base, el, bad, m, prevb, ml, u, in_pass);
             if (lane == j) mine = u;
             in_pass_mask = in_pass ? (in_pass_mask | (1ull << j)) : (in_pass_mask & ~(1ull << j));
         }
         carry_bad = mb >> 63;
     }
-    // still up at the last grid point
     for (uint64_t open = in_pass_mask; open; open &= open - 1u) {
         const unsigned j = (unsigned)__builtin_ctzll(open);
         const AzStation S = p.st[j];
         AzPassState u = az_state_of(mine, j);
-        double a[3], ad[3];
-        az_look(P, V, n - 1, S.o, a, ad);
-        u.cur.t_set_min = T[n - 1];
-        u.cur.set_azimuth_rad = a[0];
-        u.cur.flags |= AZH_PASS_UP_AT_END;
-        u.cur.grid_set = n - 1;
-        finish(S, u, j);
+        az_pass_close_at_end(row(j, S), AzLookStation{{P, V}, S.o}, u);
         if (lane == j) mine = u;
     }
     if (lane < p.n_st) p.n_passes[(size_t)(p.st0 + lane) * p.n_sats + srow] = mine.count;
