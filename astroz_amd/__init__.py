@@ -394,6 +394,49 @@ def station_passes(source, times, stations, *, min_elevation=10.0, start_time=No
     return np.concatenate(parts) if parts else np.empty(0, dtype=STATION_PASS_DTYPE)
 
 
+# eclipses(): one row per shadow interval
+ECLIPSE_DTYPE = np.dtype([("sat", "<u4"), ("entry", "<f8"), ("exit", "<f8"), ("flags", "<u4")])
+
+
+def sun_position(jd):
+    """The Sun's position at Julian date(s) ``jd`` (UTC), km, in the TEME frame of ``propagate(output="teme")``: shape
+    ``jd.shape + (3,)``.  The low-precision series of the Astronomical Almanac (0.01 degrees, 1950-2050): the model
+    :func:`eclipses` uses.  A host function; no GPU involved."""
+    return _native.sun_position(jd)
+
+
+def eclipses(source, times, *, kind="umbra", start_time=None, state=False, norad_id=None, fetch=None, allow_network=False):
+    """Earth-shadow intervals of every satellite during ``times`` (minutes from ``start_time``, default now; strictly
+    increasing).  ``kind``: ``"umbra"`` (full shadow) or ``"penumbra"`` (any shadow, the umbra included).
+
+    Returns a numpy structured array, one row per interval, sorted by (sat, entry): ``sat`` (output row), ``entry``, ``exit``
+    (minutes from ``start_time``, refined between grid points by cubic Hermite interpolation of the distance to the shadow
+    cone and its rate) and ``flags`` (1: already in shadow at the first time, 2: still in shadow at the last, 4: cut by a
+    failed propagation; an open end is the grid time).  With ``state=True`` also the ``(n_satellites, n_times)`` uint8 matrix
+    of the grid points: 0 sunlit, 1 penumbra only, 2 umbra, 255 propagation failed.  Conical shadow of a spherical Earth; no
+    oblateness, refraction or light time.  The propagation and the search run on the GPU; only the records come back."""
+    if kind not in _native.SHADOW_KINDS:
+        raise ValueError("kind must be 'umbra' or 'penumbra'")
+    minutes = np.ascontiguousarray(times, dtype=np.float64)
+    if minutes.ndim != 1 or (len(minutes) > 1 and not (np.diff(minutes) > 0).all()):
+        raise ValueError("times must be strictly increasing")
+    const = source if isinstance(source, Constellation) else Constellation(source, norad_id=norad_id, fetch=fetch,
+                                                                           allow_network=allow_network)
+    minutes, offsets, start = _minutes_and_offsets(const, minutes, start_time)
+    find = lambda room: const._dev.find_eclipses(minutes, offsets, reference_jd=start, kind=_native.SHADOW_KINDS[kind],  # noqa: E731
+                                                 max_eclipses=room, state=state)
+    res = find(32)
+    if res[1].size and int(res[1].max()) > res[0].shape[1]:  # more intervals than room: once more with room for all of them
+        res = find(int(res[1].max()))
+    rec, cnt = res[0], res[1]
+    idx = np.repeat(np.arange(len(cnt), dtype=np.intp), cnt)
+    k = np.concatenate([np.arange(c, dtype=np.intp) for c in cnt]) if len(cnt) else np.zeros(0, dtype=np.intp)
+    r = rec[idx, k] if len(idx) else rec.reshape(-1)[:0]
+    out = np.empty(len(idx), dtype=ECLIPSE_DTYPE)
+    out["sat"], out["entry"], out["exit"], out["flags"] = idx, r["t_entry_min"], r["t_exit_min"], r["flags"]
+    return (out, res[2]) if state else out
+
+
 def screen(source, times, threshold=10.0, *, target=None, start_time=None, norad_id=None, fetch=None, allow_network=False):
     """Screen a constellation for conjunction events (reference __init__.py L535-658).
 
@@ -470,7 +513,8 @@ def escape_velocity(mu, radius):
     return _scalar(_native.lib().orbital_escape_velocity(float(mu), float(radius)), "orbital_escape_velocity", "invalid radius")
 
 
-__all__ = ["__version__", "Tle", "Sgp4Constellation", "Constellation", "propagate", "passes", "station_passes", "screen",
+__all__ = ["__version__", "Tle", "Sgp4Constellation", "Constellation", "propagate", "passes", "station_passes", "eclipses",
+           "sun_position", "ECLIPSE_DTYPE", "screen",
            "coarse_screen", "set_fetcher", "celestrak_url", "WGS72", "WGS84", "hohmann_transfer", "orbital_velocity", "orbital_period",
            "escape_velocity", "EARTH_MU", "EARTH_R_EQ", "EARTH_J2", "SUN_MU", "MOON_MU"]
 # (the reference's package also re-exports bi_elliptic_transfer, lambert and propagate_numerical -- its orbital-mechanics and

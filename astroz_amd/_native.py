@@ -21,6 +21,12 @@ PASS_DTYPE = np.dtype([("t_rise_min", "<f8"), ("t_culm_min", "<f8"), ("t_set_min
                        ("rise_azimuth_rad", "<f8"), ("set_azimuth_rad", "<f8"), ("flags", "<u4"), ("grid_rise", "<u4"),
                        ("grid_culm", "<u4"), ("grid_set", "<u4")])
 PASS_UP_AT_START, PASS_UP_AT_END, PASS_CUT_BY_ERROR = 1, 2, 4
+# azh_eclipse, its flags and the shadow kinds
+ECLIPSE_DTYPE = np.dtype([("t_entry_min", "<f8"), ("t_exit_min", "<f8"), ("flags", "<u4"), ("grid_entry", "<u4"),
+                          ("grid_exit", "<u4"), ("reserved", "<u4")])
+ECLIPSE_IN_AT_START, ECLIPSE_IN_AT_END, ECLIPSE_CUT_BY_ERROR = 1, 2, 4
+SHADOW_UMBRA, SHADOW_PENUMBRA = 0, 1
+SHADOW_KINDS = {"umbra": SHADOW_UMBRA, "penumbra": SHADOW_PENUMBRA}
 
 AZ_ERR_HIP = -200
 # azh_last_path bits (include/astroz_hip.h)
@@ -47,6 +53,7 @@ EXPORTS = [
     "orbital_hohmann", "orbital_velocity", "orbital_period", "orbital_escape_velocity",
     "azh_coords_topocentric", "azh_set_observer", "azh_find_passes_host", "azh_find_passes_device",
     "azh_find_passes_stations_host", "azh_find_passes_stations_device",
+    "azh_sun_position_teme", "azh_selftest_sun", "azh_shadow_state", "azh_find_eclipses_host", "azh_find_eclipses_device",
 ]
 
 
@@ -263,6 +270,16 @@ def lib():
     L.azh_find_passes_stations_host.restype = i32
     L.azh_find_passes_stations_device.argtypes = [vp, vp, sz, vp, dbl, vp, vp, sz, vp, sz, vp, vp]
     L.azh_find_passes_stations_device.restype = i32
+    L.azh_sun_position_teme.argtypes = [dbl, vp]
+    L.azh_sun_position_teme.restype = None
+    L.azh_selftest_sun.argtypes = [vp, sz, vp, i32]
+    L.azh_selftest_sun.restype = i32
+    L.azh_shadow_state.argtypes = [vp, vp, vp, vp]
+    L.azh_shadow_state.restype = i32
+    L.azh_find_eclipses_host.argtypes = [vp, vp, sz, vp, dbl, i32, vp, sz, vp, vp]
+    L.azh_find_eclipses_host.restype = i32
+    L.azh_find_eclipses_device.argtypes = [vp, vp, sz, vp, dbl, i32, vp, sz, vp, vp, vp]
+    L.azh_find_eclipses_device.restype = i32
     L.orbital_hohmann.argtypes = [dbl, dbl, dbl, vp]
     L.orbital_hohmann.restype = i32
     for f, n in (("orbital_velocity", 3), ("orbital_period", 2), ("orbital_escape_velocity", 2)):
@@ -519,6 +536,32 @@ class DeviceConstellation:
         check(lib().azh_find_passes_stations_device(self._h, times.ctypes.data, len(times), _ptr(off), float(reference_jd),
                                                     st.ctypes.data, mk.ctypes.data, len(st), d_out, int(max_passes), d_n_passes,
                                                     stream), "azh_find_passes_stations_device")
+
+    # -- Earth shadow -----------------------------------------------------------------------------
+    def find_eclipses(self, times_min, offsets_min=None, *, reference_jd, kind=SHADOW_UMBRA, max_eclipses=32, state=False):
+        """Earth-shadow intervals (azh_find_eclipses_host): (records (n, max_eclipses) of ECLIPSE_DTYPE, n_eclipses (n,) u32 --
+        the TRUE count per satellite, which may exceed max_eclipses), and with state=True also the (n, n_times) uint8 matrix
+        (0 sunlit, 1 penumbra only, 2 umbra, 255 propagation failed).  reference_jd: the Julian date of times_min == 0."""
+        times = _f64(times_min)
+        off = None if offsets_min is None else _f64(offsets_min)
+        if off is not None and len(off) < self.n:
+            raise ValueError("epoch_offsets must have at least num_satellites elements")
+        out = np.zeros((self.n, int(max_eclipses)), dtype=ECLIPSE_DTYPE)
+        cnt = np.zeros(self.n, dtype=np.uint32)
+        st = np.zeros((self.n, len(times)), dtype=np.uint8) if state else None
+        check(lib().azh_find_eclipses_host(self._h, times.ctypes.data, len(times), _ptr(off), float(reference_jd), int(kind),
+                                           out.ctypes.data if max_eclipses else None, int(max_eclipses), cnt.ctypes.data,
+                                           st.ctypes.data if state and st.size else None), "azh_find_eclipses_host")
+        return (out, cnt, st) if state else (out, cnt)
+
+    def find_eclipses_device(self, times_min, offsets_min, d_out, max_eclipses, d_n_eclipses, *, reference_jd, kind=SHADOW_UMBRA,
+                             d_state=None, stream=None):
+        """azh_find_eclipses_device: d_out / d_n_eclipses / d_state are raw device pointers (n x max_eclipses records of
+        ECLIPSE_DTYPE, n u32, n x n_times u8 or None); asynchronous."""
+        times = _f64(times_min)
+        off = None if offsets_min is None else _f64(offsets_min)
+        check(lib().azh_find_eclipses_device(self._h, times.ctypes.data, len(times), _ptr(off), float(reference_jd), int(kind),
+                                             d_out, int(max_eclipses), d_n_eclipses, d_state, stream), "azh_find_eclipses_device")
 
     def screen_all(self, times_min, threshold=10.0, offsets_min=None, max_results=10_000_000):
         """All-vs-all: propagate on the device and screen there: (pairs (k,2) u32, t_index (k,) u32),
@@ -869,6 +912,33 @@ def selftest_math(x, device=0):
     check(lib().azh_selftest_math(x.ctypes.data, n, out.ctypes.data, device), "azh_selftest_math")
     return {"sin": out[:n], "cos": out[n:2 * n], "x_rcp": out[2 * n:3 * n], "x_rsqrt2": out[3 * n:4 * n],
             "rot_sin": out[4 * n:5 * n], "rot_cos": out[5 * n:]}
+
+
+def sun_position(jd):
+    """The Sun's TEME position in km at Julian date(s) jd (azh_sun_position_teme): shape jd.shape + (3,)."""
+    jd = np.asarray(jd, dtype=np.float64)
+    out = np.empty(jd.shape + (3,))
+    flat, v, f = out.reshape(-1, 3), np.empty(3), lib().azh_sun_position_teme
+    for k, x in enumerate(jd.reshape(-1)):
+        f(float(x), v.ctypes.data)
+        flat[k] = v
+    return out
+
+
+def selftest_sun(jd, device=0):
+    """The device function's Sun vectors (km) at Julian dates jd: (n, 3) (azh_selftest_sun)."""
+    jd = _f64(np.atleast_1d(jd))
+    out = np.empty((len(jd), 3))
+    check(lib().azh_selftest_sun(jd.ctypes.data, len(jd), out.ctypes.data, device), "azh_selftest_sun")
+    return out
+
+
+def shadow_state(r_teme, sun_km):
+    """(state, f_umbra km, f_penumbra km) of TEME position r_teme for the Sun at sun_km (azh_shadow_state)."""
+    r, s = _f64(r_teme), _f64(sun_km)
+    fu, fp = C.c_double(), C.c_double()
+    st = lib().azh_shadow_state(r.ctypes.data, s.ctypes.data, C.addressof(fu), C.addressof(fp))
+    return int(st), fu.value, fp.value
 
 
 def julian_to_gmst(jd):

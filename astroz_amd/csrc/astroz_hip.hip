@@ -25,6 +25,8 @@
 
 #include "kernels.h"
 #include "passes_kernel.h"
+#include "sun.h"
+#include "eclipse_kernel.h"
 #include "tle_host.h"
 #include "host_step.h"
 
@@ -257,6 +259,9 @@ struct azh_constellation {
     DevBuf<uint32_t> d_pass_n;
     std::vector<AzStation> h_stations;    // azh_find_passes_stations_*: the stations of the last call ...
     DevBuf<AzStation> d_stations;         // ... and their grow-only device copy
+    DevBuf<AzSunPoint> d_sun;             // azh_find_eclipses_*: the call's Sun table (one record per grid time) ...
+    DevBuf<azh_eclipse> d_ecl_out;        // ... and the records / state matrix of azh_find_eclipses_host (counts: d_pass_n)
+    DevBuf<unsigned char> d_ecl_state;
     unsigned cached_n_times = 0;
     int cached_mode = 0;
     unsigned off_cat = 0; // d_list + off_cat: near-earth members in plain catalog order (k_tiles_fast: runs of consecutive rows)
@@ -2718,6 +2723,111 @@ int32_t azh_find_passes_stations_host(azh_constellation *c, const double *times,
             return find_passes_stations(c, times, n_times, offsets, reference_jd, stations_lla, min_elevation_deg, n_stations, d_out,
                                         max_passes, d_n, c->s_main);
         });
+    });
+}
+
+// ---- the Sun, the Earth's shadow, eclipse intervals ----------------------------------------------------------------------
+void azh_sun_position_teme(double jd, double sun_km[3])
+{
+    if (!sun_km) return;
+    az_sun_model(jd, sun_km, [](double a, double &sn, double &cs) { sn = std::sin(a); cs = std::cos(a); });
+}
+
+int32_t azh_shadow_state(const double r_teme[3], const double sun_km[3], double *f_umbra, double *f_penumbra)
+{
+    if (!r_teme || !sun_km) return -1;
+    auto rsqrt = [](double x) { return 1.0 / std::sqrt(x); };
+    const AzShadow o = az_shadow(r_teme, az_sun_point(sun_km, rsqrt), rsqrt);
+    if (f_umbra) *f_umbra = o.fu;
+    if (f_penumbra) *f_penumbra = o.fp;
+    return az_shadow_state(o);
+}
+
+int32_t azh_selftest_sun(const double *jd, size_t n, double *out3n, int32_t device)
+{
+    if (!jd || !out3n) return AZ_ERR_NULL_POINTER;
+    if (n == 0) return AZ_OK;
+    if (n > 0xffffffffu / 4) return AZ_ERR_VALUE;
+    HIP_TRY(hipSetDevice(device));
+    DevBuf<double> d;
+    if (d.ensure(4 * n) != AZ_OK) return AZ_ERR_HIP;
+    if (!hip_ok(hipMemcpy(d.p, jd, sizeof(double) * n, hipMemcpyHostToDevice), "H2D")) return AZ_ERR_HIP;
+    hipLaunchKernelGGL(k_sun_kat, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, nullptr, d.p, (unsigned)n, d.p + n);
+    if (!hip_ok(hipGetLastError(), "k_sun_kat") ||
+        !hip_ok(hipMemcpy(out3n, d.p + n, sizeof(double) * 3 * n, hipMemcpyDeviceToHost), "D2H"))
+        return AZ_ERR_HIP;
+    return AZ_OK;
+}
+
+// azh_find_eclipses_*: TEME states with velocities in the pass finders' scratch, the Sun table behind the staged time axis,
+// k_eclipses behind every window's propagation
+static int32_t find_eclipses(azh_constellation *c, const double *times, size_t n_times, const double *offsets, double reference_jd,
+                             int32_t kind, azh_eclipse *d_out, size_t max_eclipses, uint32_t *d_n, uint8_t *d_state, hipStream_t st)
+{
+    if (!(reference_jd > 0.0) || !std::isfinite(reference_jd) || (kind != AZH_SHADOW_UMBRA && kind != AZH_SHADOW_PENUMBRA) ||
+        max_eclipses > 0xffffffffu || !times_increasing(times, n_times))
+        return AZ_ERR_VALUE;
+    if (c->n == 0) return AZ_OK;
+    if (c->d_sun.cap < n_times) HIP_TRY(hipStreamSynchronize(st)); // (a scan in flight reads it)
+    if (c->d_sun.ensure(n_times) != AZ_OK) return AZ_ERR_HIP;
+    return pass_windows(c, times, n_times, offsets, reference_jd, AZ_OUT_TEME, d_n, c->n, st, [&](size_t lo, size_t hi) -> int32_t {
+        if (lo == 0) { // (the time axis is on the device from here on)
+            hipLaunchKernelGGL(k_sun_table, dim3((unsigned)((n_times + 63) / 64)), dim3(64), 0, st, c->d_times.p, (unsigned)n_times,
+                               reference_jd, c->d_sun.p);
+            HIP_TRY(hipGetLastError());
+        }
+        EclipseArgs q{};
+        q.pos = c->d_pass_pos.p; q.vel = c->d_pass_vel.p; q.err = c->d_pass_err.p;
+        q.times = c->d_times.p; q.sun = c->d_sun.p; q.n_times = (unsigned)n_times;
+        q.row0 = (unsigned)lo; q.n_rows = (unsigned)(hi - lo);
+        q.penumbra = kind == AZH_SHADOW_PENUMBRA;
+        q.out = d_out; q.max_eclipses = (unsigned)max_eclipses; q.n_eclipses = d_n; q.state = d_state;
+        hipLaunchKernelGGL(k_eclipses, dim3((unsigned)((hi - lo + AZ_ECLIPSE_WAVES - 1) / AZ_ECLIPSE_WAVES)), dim3(64 * AZ_ECLIPSE_WAVES), 0,
+                           st, q);
+        HIP_TRY(hipGetLastError());
+        return AZ_OK;
+    });
+}
+
+int32_t azh_find_eclipses_device(azh_constellation *c, const double *times, size_t n_times, const double *offsets, double reference_jd,
+                                 int32_t kind, azh_eclipse *d_out, size_t max_eclipses, uint32_t *d_n_eclipses, uint8_t *d_state,
+                                 void *stream)
+{
+    return guarded([&]() -> int32_t {
+        if (!c || !d_n_eclipses || (n_times && !times) || (max_eclipses && !d_out)) return AZ_ERR_NULL_POINTER;
+        if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
+        return find_eclipses(c, times, n_times, offsets, reference_jd, kind, d_out, max_eclipses, d_n_eclipses, d_state,
+                             stream ? (hipStream_t)stream : c->s_main);
+    });
+}
+
+int32_t azh_find_eclipses_host(azh_constellation *c, const double *times, size_t n_times, const double *offsets, double reference_jd,
+                               int32_t kind, azh_eclipse *out, size_t max_eclipses, uint32_t *n_eclipses, uint8_t *state)
+{
+    return guarded([&]() -> int32_t {
+        if (!c || !n_eclipses || (n_times && !times) || (max_eclipses && !out)) return AZ_ERR_NULL_POINTER;
+        if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
+        size_t n_rec, n_state, bytes;
+        if (__builtin_mul_overflow(c->n, max_eclipses, &n_rec) || __builtin_mul_overflow(n_rec, sizeof(azh_eclipse), &bytes) ||
+            __builtin_mul_overflow(c->n, n_times, &n_state))
+            return AZ_ERR_VALUE;
+        if (!state) n_state = 0;
+        if (c->n == 0) return find_eclipses(c, times, n_times, offsets, reference_jd, kind, nullptr, max_eclipses, nullptr, nullptr, c->s_main);
+        if (c->d_ecl_out.cap < n_rec || c->d_pass_n.cap < c->n || c->d_ecl_state.cap < n_state) HIP_TRY(hipStreamSynchronize(c->s_main));
+        if ((n_rec && c->d_ecl_out.ensure(n_rec) != AZ_OK) || c->d_pass_n.ensure(c->n) != AZ_OK ||
+            (n_state && c->d_ecl_state.ensure(n_state) != AZ_OK))
+            return AZ_ERR_HIP;
+        // (the first failure wins; the final sync always runs)
+        int32_t rc = find_eclipses(c, times, n_times, offsets, reference_jd, kind, n_rec ? c->d_ecl_out.p : nullptr, max_eclipses,
+                                   c->d_pass_n.p, n_state ? c->d_ecl_state.p : nullptr, c->s_main);
+        auto back = [&](void *dst, const void *src, size_t nbytes) {
+            if (rc == AZ_OK && nbytes && !hip_ok(hipMemcpyAsync(dst, src, nbytes, hipMemcpyDeviceToHost, c->s_main), "D2H")) rc = AZ_ERR_HIP;
+        };
+        back(n_eclipses, c->d_pass_n.p, sizeof(uint32_t) * c->n);
+        back(out, c->d_ecl_out.p, sizeof(azh_eclipse) * n_rec);
+        back(state, c->d_ecl_state.p, n_state);
+        if (!hip_ok(hipStreamSynchronize(c->s_main), "sync") && rc == AZ_OK) rc = AZ_ERR_HIP;
+        return rc;
     });
 }
 

@@ -174,6 +174,29 @@ pub extern "c" fn azh_find_passes_stations_device(h: ?*Handle, times_min: [*]con
     epoch_offsets_min: ?[*]const f64, reference_jd: f64, stations_lla: [*]const [3]f64, min_elevation_deg: [*]const f64,
     n_stations: usize, d_out: [*]Pass, max_passes: usize, d_n_passes: [*]u32, stream: ?*anyopaque) i32;
 
+// the Sun, the Earth's shadow and eclipse intervals
+pub extern "c" fn azh_sun_position_teme(jd: f64, sun_km: *[3]f64) void; // Almanac low-precision series (Vallado, "Sun"), km
+pub extern "c" fn azh_selftest_sun(jd: [*]const f64, n: usize, out3n: [*]f64, device: i32) i32; // the device twin (KAT)
+pub extern "c" fn azh_shadow_state(r_teme: *const [3]f64, sun_km: *const [3]f64, f_umbra: ?*f64, f_penumbra: ?*f64) i32; // 0 sunlit, 1 penumbra, 2 umbra
+pub const Eclipse = extern struct {
+    t_entry_min: f64,
+    t_exit_min: f64,
+    flags: u32, // ECLIPSE_*
+    grid_entry: u32,
+    grid_exit: u32,
+    reserved: u32,
+};
+pub const ECLIPSE_IN_AT_START: u32 = 1;
+pub const ECLIPSE_IN_AT_END: u32 = 2;
+pub const ECLIPSE_CUT_BY_ERROR: u32 = 4;
+pub const SHADOW_UMBRA: i32 = 0;
+pub const SHADOW_PENUMBRA: i32 = 1;
+pub extern "c" fn azh_find_eclipses_host(h: ?*Handle, times_min: [*]const f64, n_times: usize, epoch_offsets_min: ?[*]const f64,
+    reference_jd: f64, kind: i32, out: ?[*]Eclipse, max_eclipses: usize, n_eclipses: [*]u32, state_or_null: ?[*]u8) i32;
+pub extern "c" fn azh_find_eclipses_device(h: ?*Handle, times_min: [*]const f64, n_times: usize, epoch_offsets_min: ?[*]const f64,
+    reference_jd: f64, kind: i32, d_out: ?[*]Eclipse, max_eclipses: usize, d_n_eclipses: [*]u32, d_state_or_null: ?[*]u8,
+    stream: ?*anyopaque) i32;
+
 // one process, several devices: replaces the std.Thread fan-out of Constellation.propagateConstellation
 // (src/Constellation.zig L557-603)
 pub const Group = opaque {};

@@ -297,6 +297,53 @@ int32_t azh_find_passes_stations_device(azh_constellation *c, const double *time
                                         const double *min_elevation_deg, size_t n_stations, azh_pass *d_out, size_t max_passes,
                                         uint32_t *d_n_passes, void *stream);
 
+/* The Sun's position (no reference counterpart): the low-precision series of the Astronomical Almanac as Vallado gives it
+ * (algorithm "Sun"; 0.01 degrees, 1950-2050), km, for the Julian date jd.  jd is taken as UTC (UT1 and TT are not told apart)
+ * and the mean-of-date vector is used as TEME; both are below the series' own 0.01 degrees.  Pure host function: the twin of
+ * the device function the eclipse finder uses. */
+void azh_sun_position_teme(double jd, double sun_km[3]);
+/* Device known answers of the same model: out3n[3 i ..] = the device function's Sun vector (km) at jd[i]; one launch on
+ * `device`. */
+int32_t azh_selftest_sun(const double *jd, size_t n, double *out3n, int32_t device);
+
+/* Earth shadow at TEME position r_teme (km) for the Sun at sun_km: conical umbra / penumbra of a spherical Earth (6378.137 km)
+ * and Sun (696,000 km).  With s the unit vector to the Sun, x = -r.s and h the distance from the shadow axis,
+ *   f_umbra = h - (R - x tan a_u), sin a_u = (R_sun - R) / d;   f_penumbra = h - (R + x tan a_p), sin a_p = (R_sun + R) / d
+ * (km; either pointer may be NULL).  Returns 0 sunlit, 1 penumbra only, 2 umbra: in a shadow <=> x > 0 and f < 0.  Oblateness,
+ * refraction and light time are not modelled.  Pure host function, the twin of the kernel's arithmetic; NULL vectors -> -1. */
+int32_t azh_shadow_state(const double r_teme[3], const double sun_km[3], double *f_umbra, double *f_penumbra);
+
+/* Eclipse intervals (no reference counterpart): when every satellite is inside the Earth's shadow over the grid times_min
+ * (strictly increasing, else AZ_ERR_VALUE; tsince as azh_propagate_*).  reference_jd is the Julian date of times_min == 0 and
+ * places the Sun: reference_jd <= 0 (or not a number) -> AZ_ERR_VALUE.  kind: AZH_SHADOW_UMBRA or AZH_SHADOW_PENUMBRA (any
+ * shadow: f_penumbra < 0); anything else -> AZ_ERR_VALUE.
+ * The handle is propagated in AZ_OUT_TEME with velocities into the pass finders' device scratch (row windows of at most
+ * ~512 MiB), a small kernel tabulates the Sun per grid time, and a kernel scans each row: in[i] = (no propagation error at i)
+ * && x > 0 && f < 0; entries / exits are its 0 -> 1 / 1 -> 0 transitions.  Entry and exit times are the root of the cubic
+ * Hermite interpolant of f (values and rates at the two bracketing grid points, the Sun's motion over the interval included)
+ * in that interval.  Nothing is propagated again.  An interval shorter than the grid step that holds no grid point is not seen.
+ * out: n_sats x max_eclipses records, the first max_eclipses intervals of satellite s at out[s * max_eclipses ...], in time
+ * order; n_eclipses[s] = the TRUE number (may exceed max_eclipses); max_eclipses == 0 counts only.  grid_entry / grid_exit =
+ * first / last grid index inside.  state (may be NULL): n_sats x n_times bytes, satellite-major, whatever the kind: 0 sunlit,
+ * 1 penumbra only, 2 umbra, 255 where propagation failed.  Deep-space members take part like any other row.
+ * _device: out / n_eclipses / state on c's device, asynchronous on `stream` (NULL = the handle's). */
+typedef struct azh_eclipse {
+    double t_entry_min, t_exit_min; /* on the caller's time axis (times_min), refined (above) */
+    uint32_t flags;                 /* AZH_ECLIPSE_* */
+    uint32_t grid_entry, grid_exit; /* first / last grid index inside the shadow */
+    uint32_t reserved;
+} azh_eclipse;
+#define AZH_ECLIPSE_IN_AT_START 1u  /* in shadow at times_min[0]: entry = first grid time, not refined */
+#define AZH_ECLIPSE_IN_AT_END 2u    /* still in shadow at the last grid time: exit = last grid time, not refined */
+#define AZH_ECLIPSE_CUT_BY_ERROR 4u /* begun or ended next to a grid point where propagation failed: that end is the grid time */
+enum { AZH_SHADOW_UMBRA = 0, AZH_SHADOW_PENUMBRA = 1 };
+int32_t azh_find_eclipses_host(azh_constellation *c, const double *times_min, size_t n_times, const double *epoch_offsets_min,
+                               double reference_jd, int32_t kind, azh_eclipse *out, size_t max_eclipses, uint32_t *n_eclipses,
+                               uint8_t *state_or_null);
+int32_t azh_find_eclipses_device(azh_constellation *c, const double *times_min, size_t n_times, const double *epoch_offsets_min,
+                                 double reference_jd, int32_t kind, azh_eclipse *d_out, size_t max_eclipses,
+                                 uint32_t *d_n_eclipses, uint8_t *d_state_or_null, void *stream);
+
 /* Fused single-target conjunction screen = Constellation.screenConstellation
  * (src/Constellation.zig L683-756; Python: Sgp4Constellation.screen_conjunction,
  * bindings/python/astroz/__init__.py L625-632).  For every satellite the minimum distance (km) to
