@@ -437,6 +437,60 @@ def eclipses(source, times, *, kind="umbra", start_time=None, state=False, norad
     return (out, res[2]) if state else out
 
 
+# access(): one row per line-of-sight window
+ACCESS_DTYPE = np.dtype([("sat", "<u4"), ("start", "<f8"), ("end", "<f8"), ("min_range", "<f8"), ("t_min_range", "<f8"),
+                         ("flags", "<u4")])
+
+
+def access(source, times, target, *, grazing_altitude=0.0, max_range=None, start_time=None, state=False, norad_id=None, fetch=None,
+           allow_network=False):
+    """Line-of-sight access windows between satellite ``target`` (an output row, as for ``screen()``) and every other
+    satellite during ``times`` (minutes from ``start_time``, default now; strictly increasing): the straight line between the
+    two stays at least ``grazing_altitude`` km above a spherical Earth of 6378.137 km and, with ``max_range`` (km) set, is no
+    longer than that.
+
+    Returns a numpy structured array, one row per window, sorted by (sat, start): ``sat`` (output row), ``start``, ``end``
+    (minutes from ``start_time``, refined between grid points by cubic Hermite interpolation of the clearance -- or the range
+    margin -- and its rate), ``min_range`` (km, the smallest distance at a grid time inside the window) and ``t_min_range``
+    (that grid time), and ``flags`` (1: already in access at the first time, 2: still in access at the last, 4: cut by a
+    failed propagation of either satellite; an open end is the grid time).  The target's own row has no windows.  With
+    ``state=True`` also the ``(n_satellites, n_times)`` uint8 matrix of the grid points: 0 Earth in the way, 1 clear line but
+    beyond ``max_range``, 2 access, 255 propagation failed.  No oblateness, refraction or light time.  The propagation and the
+    search run on the GPU; only the records come back."""
+    try:
+        row = int(target)
+    except (TypeError, ValueError):
+        raise ValueError("target must be the index of a satellite") from None
+    if row < 0 or row != target:
+        raise ValueError("target must be the index of a satellite")
+    h = float(grazing_altitude)
+    if not (np.isfinite(h) and h >= 0.0):
+        raise ValueError("grazing_altitude must be finite and >= 0 km")
+    if max_range is not None and not float(max_range) > 0.0:
+        raise ValueError("max_range must be > 0 km, or None for no limit")
+    minutes = np.ascontiguousarray(times, dtype=np.float64)
+    if minutes.ndim != 1 or (len(minutes) > 1 and not (np.diff(minutes) > 0).all()):
+        raise ValueError("times must be strictly increasing")
+    const = source if isinstance(source, Constellation) else Constellation(source, norad_id=norad_id, fetch=fetch,
+                                                                           allow_network=allow_network)
+    if row >= const.num_satellites:
+        raise ValueError("target index out of range")
+    minutes, offsets, start = _minutes_and_offsets(const, minutes, start_time)
+    find = lambda room: const._dev.find_access(minutes, row, offsets, grazing_alt_km=h, max_range_km=max_range,  # noqa: E731
+                                               max_windows=room, state=state)
+    res = find(32)
+    if res[1].size and int(res[1].max()) > res[0].shape[1]:  # more windows than room: once more with room for all of them
+        res = find(int(res[1].max()))
+    rec, cnt = res[0], res[1]
+    idx = np.repeat(np.arange(len(cnt), dtype=np.intp), cnt)
+    k = np.concatenate([np.arange(c, dtype=np.intp) for c in cnt]) if len(cnt) else np.zeros(0, dtype=np.intp)
+    r = rec[idx, k] if len(idx) else rec.reshape(-1)[:0]
+    out = np.empty(len(idx), dtype=ACCESS_DTYPE)
+    out["sat"], out["start"], out["end"], out["flags"] = idx, r["t_start_min"], r["t_end_min"], r["flags"]
+    out["min_range"], out["t_min_range"] = r["min_range_km"], minutes[r["grid_min_range"]] if len(idx) else 0.0
+    return (out, res[2]) if state else out
+
+
 def screen(source, times, threshold=10.0, *, target=None, start_time=None, norad_id=None, fetch=None, allow_network=False):
     """Screen a constellation for conjunction events (reference __init__.py L535-658).
 
@@ -514,7 +568,7 @@ def escape_velocity(mu, radius):
 
 
 __all__ = ["__version__", "Tle", "Sgp4Constellation", "Constellation", "propagate", "passes", "station_passes", "eclipses",
-           "sun_position", "ECLIPSE_DTYPE", "screen",
+           "sun_position", "ECLIPSE_DTYPE", "access", "ACCESS_DTYPE", "screen",
            "coarse_screen", "set_fetcher", "celestrak_url", "WGS72", "WGS84", "hohmann_transfer", "orbital_velocity", "orbital_period",
            "escape_velocity", "EARTH_MU", "EARTH_R_EQ", "EARTH_J2", "SUN_MU", "MOON_MU"]
 # (the reference's package also re-exports bi_elliptic_transfer, lambert and propagate_numerical -- its orbital-mechanics and

@@ -27,6 +27,10 @@ ECLIPSE_DTYPE = np.dtype([("t_entry_min", "<f8"), ("t_exit_min", "<f8"), ("flags
 ECLIPSE_IN_AT_START, ECLIPSE_IN_AT_END, ECLIPSE_CUT_BY_ERROR = 1, 2, 4
 SHADOW_UMBRA, SHADOW_PENUMBRA = 0, 1
 SHADOW_KINDS = {"umbra": SHADOW_UMBRA, "penumbra": SHADOW_PENUMBRA}
+# azh_access and its flags
+ACCESS_DTYPE = np.dtype([("t_start_min", "<f8"), ("t_end_min", "<f8"), ("min_range_km", "<f8"), ("flags", "<u4"),
+                         ("grid_start", "<u4"), ("grid_end", "<u4"), ("grid_min_range", "<u4")])
+ACCESS_OPEN_AT_START, ACCESS_OPEN_AT_END, ACCESS_CUT_BY_ERROR = 1, 2, 4
 
 AZ_ERR_HIP = -200
 # azh_last_path bits (include/astroz_hip.h)
@@ -54,6 +58,7 @@ EXPORTS = [
     "azh_coords_topocentric", "azh_set_observer", "azh_find_passes_host", "azh_find_passes_device",
     "azh_find_passes_stations_host", "azh_find_passes_stations_device",
     "azh_sun_position_teme", "azh_selftest_sun", "azh_shadow_state", "azh_find_eclipses_host", "azh_find_eclipses_device",
+    "azh_line_of_sight", "azh_find_access_host", "azh_find_access_device", "azh_find_access_track_device",
 ]
 
 
@@ -280,6 +285,14 @@ def lib():
     L.azh_find_eclipses_host.restype = i32
     L.azh_find_eclipses_device.argtypes = [vp, vp, sz, vp, dbl, i32, vp, sz, vp, vp, vp]
     L.azh_find_eclipses_device.restype = i32
+    L.azh_line_of_sight.argtypes = [vp, vp, dbl, vp, vp]
+    L.azh_line_of_sight.restype = i32
+    L.azh_find_access_host.argtypes = [vp, vp, sz, vp, sz, dbl, dbl, vp, sz, vp, vp]
+    L.azh_find_access_host.restype = i32
+    L.azh_find_access_device.argtypes = [vp, vp, sz, vp, sz, dbl, dbl, vp, sz, vp, vp, vp]
+    L.azh_find_access_device.restype = i32
+    L.azh_find_access_track_device.argtypes = [vp, vp, sz, vp, vp, vp, sz, dbl, dbl, vp, sz, vp, vp, vp]
+    L.azh_find_access_track_device.restype = i32
     L.orbital_hohmann.argtypes = [dbl, dbl, dbl, vp]
     L.orbital_hohmann.restype = i32
     for f, n in (("orbital_velocity", 3), ("orbital_period", 2), ("orbital_escape_velocity", 2)):
@@ -562,6 +575,47 @@ class DeviceConstellation:
         off = None if offsets_min is None else _f64(offsets_min)
         check(lib().azh_find_eclipses_device(self._h, times.ctypes.data, len(times), _ptr(off), float(reference_jd), int(kind),
                                              d_out, int(max_eclipses), d_n_eclipses, d_state, stream), "azh_find_eclipses_device")
+
+    # -- line-of-sight access ---------------------------------------------------------------------
+    def find_access(self, times_min, target, offsets_min=None, *, grazing_alt_km=0.0, max_range_km=None, max_windows=32,
+                    state=False):
+        """Access windows of every member to member `target` (azh_find_access_host): (records (n, max_windows) of ACCESS_DTYPE,
+        n_windows (n,) u32 -- the TRUE count per satellite, which may exceed max_windows), and with state=True also the
+        (n, n_times) uint8 matrix (0 Earth in the way, 1 clear but beyond max_range_km, 2 access, 255 either object failed).
+        max_range_km None: no range limit."""
+        times = _f64(times_min)
+        off = None if offsets_min is None else _f64(offsets_min)
+        if off is not None and len(off) < self.n:
+            raise ValueError("epoch_offsets must have at least num_satellites elements")
+        out = np.zeros((self.n, int(max_windows)), dtype=ACCESS_DTYPE)
+        cnt = np.zeros(self.n, dtype=np.uint32)
+        st = np.zeros((self.n, len(times)), dtype=np.uint8) if state else None
+        check(lib().azh_find_access_host(self._h, times.ctypes.data, len(times), _ptr(off), int(target), float(grazing_alt_km),
+                                         _max_range(max_range_km), out.ctypes.data if max_windows else None, int(max_windows),
+                                         cnt.ctypes.data, st.ctypes.data if state and st.size else None), "azh_find_access_host")
+        return (out, cnt, st) if state else (out, cnt)
+
+    def find_access_device(self, times_min, target, offsets_min, d_out, max_windows, d_n_windows, *, grazing_alt_km=0.0,
+                           max_range_km=None, d_state=None, stream=None):
+        """azh_find_access_device: d_out / d_n_windows / d_state are raw device pointers (n x max_windows records of
+        ACCESS_DTYPE, n u32, n x n_times u8 or None); asynchronous."""
+        times = _f64(times_min)
+        off = None if offsets_min is None else _f64(offsets_min)
+        check(lib().azh_find_access_device(self._h, times.ctypes.data, len(times), _ptr(off), int(target), float(grazing_alt_km),
+                                           _max_range(max_range_km), d_out, int(max_windows), d_n_windows, d_state, stream),
+              "azh_find_access_device")
+
+    def find_access_track_device(self, times_min, d_track_pos, d_track_vel, offsets_min, d_out, max_windows, d_n_windows, *,
+                                 exclude=None, grazing_alt_km=0.0, max_range_km=None, d_state=None, stream=None):
+        """azh_find_access_track_device: the same against an EXTERNAL track, d_track_pos / d_track_vel = raw device pointers to
+        (n_times, 3) float64 TEME km and km/s; exclude: a member that reports nothing (the target itself, when this handle
+        owns it)."""
+        times = _f64(times_min)
+        off = None if offsets_min is None else _f64(offsets_min)
+        ex = C.c_size_t(-1).value if exclude is None else int(exclude)
+        check(lib().azh_find_access_track_device(self._h, times.ctypes.data, len(times), _ptr(off), d_track_pos, d_track_vel, ex,
+                                                 float(grazing_alt_km), _max_range(max_range_km), d_out, int(max_windows),
+                                                 d_n_windows, d_state, stream), "azh_find_access_track_device")
 
     def screen_all(self, times_min, threshold=10.0, offsets_min=None, max_results=10_000_000):
         """All-vs-all: propagate on the device and screen there: (pairs (k,2) u32, t_index (k,) u32),
@@ -939,6 +993,20 @@ def shadow_state(r_teme, sun_km):
     fu, fp = C.c_double(), C.c_double()
     st = lib().azh_shadow_state(r.ctypes.data, s.ctypes.data, C.addressof(fu), C.addressof(fp))
     return int(st), fu.value, fp.value
+
+
+def _max_range(max_range_km):
+    """max_range_km as the C ABI takes it: None is +infinity (no limit)."""
+    return float("inf") if max_range_km is None else float(max_range_km)
+
+
+def line_of_sight(r1, r2, grazing_alt_km=0.0):
+    """(clear, clearance km, range km) of the segment between TEME positions r1 and r2 (azh_line_of_sight): clear is True
+    when the segment stays at least grazing_alt_km above a spherical Earth of 6378.137 km."""
+    a, b = _f64(r1), _f64(r2)
+    cl, rg = C.c_double(), C.c_double()
+    ok = lib().azh_line_of_sight(a.ctypes.data, b.ctypes.data, float(grazing_alt_km), C.addressof(cl), C.addressof(rg))
+    return bool(ok), cl.value, rg.value
 
 
 def julian_to_gmst(jd):

@@ -27,6 +27,8 @@
 #include "passes_kernel.h"
 #include "sun.h"
 #include "eclipse_kernel.h"
+#include "los.h"
+#include "access_kernel.h"
 #include "tle_host.h"
 #include "host_step.h"
 
@@ -262,6 +264,9 @@ struct azh_constellation {
     DevBuf<AzSunPoint> d_sun;             // azh_find_eclipses_*: the call's Sun table (one record per grid time) ...
     DevBuf<azh_eclipse> d_ecl_out;        // ... and the records / state matrix of azh_find_eclipses_host (counts: d_pass_n)
     DevBuf<unsigned char> d_ecl_state;
+    DevBuf<double> d_acc_track;           // azh_find_access_host / _device: the target's own track -- positions, velocities, error bytes ...
+    DevBuf<azh_access> d_acc_out;         // ... and the records / state matrix of azh_find_access_host (counts: d_pass_n)
+    DevBuf<unsigned char> d_acc_state;
     unsigned cached_n_times = 0;
     int cached_mode = 0;
     unsigned off_cat = 0; // d_list + off_cat: near-earth members in plain catalog order (k_tiles_fast: runs of consecutive rows)
@@ -2826,6 +2831,125 @@ int32_t azh_find_eclipses_host(azh_constellation *c, const double *times, size_t
         back(n_eclipses, c->d_pass_n.p, sizeof(uint32_t) * c->n);
         back(out, c->d_ecl_out.p, sizeof(azh_eclipse) * n_rec);
         back(state, c->d_ecl_state.p, n_state);
+        if (!hip_ok(hipStreamSynchronize(c->s_main), "sync") && rc == AZ_OK) rc = AZ_ERR_HIP;
+        return rc;
+    });
+}
+
+// ---- line of sight, access windows ---------------------------------------------------------------------------------------
+int32_t azh_line_of_sight(const double r1[3], const double r2[3], double grazing_alt_km, double *clearance_km, double *range_km)
+{
+    if (!r1 || !r2) return -1;
+    const AzLos o = az_los(r1, r2, [](double x) { return 1.0 / std::sqrt(x); });
+    if (clearance_km) *clearance_km = o.clearance;
+    if (range_km) *range_km = o.range;
+    return o.clearance - (AZ_LOS_R_EARTH + grazing_alt_km) >= 0.0 ? 1 : 0;
+}
+
+// the argument rules of the three variants that need neither the handle nor a device
+static int32_t access_args(const double *times, size_t n_times, double grazing_alt_km, double max_range_km, size_t max_windows)
+{
+    if (!std::isfinite(grazing_alt_km) || grazing_alt_km < 0.0 || !(max_range_km > 0.0) || max_windows > 0xffffffffu) return AZ_ERR_VALUE;
+    return !times || times_increasing(times, n_times) ? AZ_OK : AZ_ERR_VALUE;
+}
+
+// azh_find_access_*: TEME states with velocities in the pass finders' scratch, k_access behind every window's propagation.
+// The target is an external track (`external`: d_tpos / d_tvel; `target` = the member to leave out or kNoTarget), or member
+// `target`, whose track -- positions, velocities, error bytes -- a one-row window launch behind the staged time axis puts into
+// d_acc_track.
+static int32_t find_access(azh_constellation *c, const double *times, size_t n_times, const double *offsets, size_t target, bool external,
+                           const double *d_tpos, const double *d_tvel, double grazing_alt_km, double max_range_km, azh_access *d_out,
+                           size_t max_windows, uint32_t *d_n, uint8_t *d_state, hipStream_t st)
+{
+    if (external ? (target != kNoTarget && target >= c->n) : target >= c->n) return AZ_ERR_VALUE;
+    if (c->n == 0) return AZ_OK;
+    const unsigned char *d_terr = nullptr;
+    if (!external && n_times) {
+        const size_t words = 6 * n_times + (n_times + 7) / 8;
+        if (c->d_acc_track.cap < words) HIP_TRY(hipStreamSynchronize(st)); // (a scan in flight reads it)
+        if (c->d_acc_track.ensure(words) != AZ_OK) return AZ_ERR_HIP;
+        d_tpos = c->d_acc_track.p;
+        d_tvel = c->d_acc_track.p + 3 * n_times;
+        d_terr = reinterpret_cast<const unsigned char *>(c->d_acc_track.p + 6 * n_times);
+    }
+    return pass_windows(c, times, n_times, offsets, 0.0, AZ_OUT_TEME, d_n, c->n, st, [&](size_t lo, size_t hi) -> int32_t {
+        if (lo == 0 && d_terr) { // (the time axis is on the device from here on) row `target` of arrays based `target` rows earlier
+            const size_t shift = target * n_times;
+            const uintptr_t pb = reinterpret_cast<uintptr_t>(d_tpos) - 3 * shift * sizeof(double);
+            const uintptr_t vb = reinterpret_cast<uintptr_t>(d_tvel) - 3 * shift * sizeof(double);
+            const uintptr_t eb = reinterpret_cast<uintptr_t>(d_terr) - shift;
+            if (int32_t rc = launch_all(c, reinterpret_cast<double *>(pb), reinterpret_cast<double *>(vb), AZ_LAYOUT_SAT_MAJOR, 0,
+                                        reinterpret_cast<uint8_t *>(eb), st, 0, target, target + 1);
+                rc != AZ_OK)
+                return rc;
+        }
+        AccessArgs q{};
+        q.pos = c->d_pass_pos.p; q.vel = c->d_pass_vel.p; q.err = c->d_pass_err.p;
+        q.times = c->d_times.p; q.tpos = d_tpos; q.tvel = d_tvel; q.terr = d_terr; q.n_times = (unsigned)n_times;
+        q.row0 = (unsigned)lo; q.n_rows = (unsigned)(hi - lo);
+        q.skip_row = target == kNoTarget ? 0xffffffffu : (unsigned)target;
+        q.r_graze = AZ_LOS_R_EARTH + grazing_alt_km; q.max_range = max_range_km;
+        q.out = d_out; q.max_windows = (unsigned)max_windows; q.n_windows = d_n; q.state = d_state;
+        hipLaunchKernelGGL(k_access, dim3((unsigned)((hi - lo + AZ_ACCESS_WAVES - 1) / AZ_ACCESS_WAVES)), dim3(64 * AZ_ACCESS_WAVES), 0, st, q);
+        HIP_TRY(hipGetLastError());
+        return AZ_OK;
+    });
+}
+
+int32_t azh_find_access_track_device(azh_constellation *c, const double *times, size_t n_times, const double *offsets,
+                                     const double *d_track_pos, const double *d_track_vel, size_t exclude_index, double grazing_alt_km,
+                                     double max_range_km, azh_access *d_out, size_t max_windows, uint32_t *d_n_windows, uint8_t *d_state,
+                                     void *stream)
+{
+    return guarded([&]() -> int32_t {
+        if (int32_t rc = access_args(times, n_times, grazing_alt_km, max_range_km, max_windows); rc != AZ_OK) return rc;
+        if (!c || !d_n_windows || (n_times && (!times || !d_track_pos || !d_track_vel)) || (max_windows && !d_out)) return AZ_ERR_NULL_POINTER;
+        if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
+        return find_access(c, times, n_times, offsets, exclude_index, true, d_track_pos, d_track_vel, grazing_alt_km, max_range_km, d_out,
+                           max_windows, d_n_windows, d_state, stream ? (hipStream_t)stream : c->s_main);
+    });
+}
+
+int32_t azh_find_access_device(azh_constellation *c, const double *times, size_t n_times, const double *offsets, size_t target_index,
+                               double grazing_alt_km, double max_range_km, azh_access *d_out, size_t max_windows, uint32_t *d_n_windows,
+                               uint8_t *d_state, void *stream)
+{
+    return guarded([&]() -> int32_t {
+        if (int32_t rc = access_args(times, n_times, grazing_alt_km, max_range_km, max_windows); rc != AZ_OK) return rc;
+        if (!c || !d_n_windows || (n_times && !times) || (max_windows && !d_out)) return AZ_ERR_NULL_POINTER;
+        if (target_index >= c->n) return AZ_ERR_VALUE;
+        if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
+        return find_access(c, times, n_times, offsets, target_index, false, nullptr, nullptr, grazing_alt_km, max_range_km, d_out, max_windows,
+                           d_n_windows, d_state, stream ? (hipStream_t)stream : c->s_main);
+    });
+}
+
+int32_t azh_find_access_host(azh_constellation *c, const double *times, size_t n_times, const double *offsets, size_t target_index,
+                             double grazing_alt_km, double max_range_km, azh_access *out, size_t max_windows, uint32_t *n_windows,
+                             uint8_t *state)
+{
+    return guarded([&]() -> int32_t {
+        if (int32_t rc = access_args(times, n_times, grazing_alt_km, max_range_km, max_windows); rc != AZ_OK) return rc;
+        if (!c || !n_windows || (n_times && !times) || (max_windows && !out)) return AZ_ERR_NULL_POINTER;
+        size_t n_rec, n_state, bytes;
+        if (target_index >= c->n || __builtin_mul_overflow(c->n, max_windows, &n_rec) ||
+            __builtin_mul_overflow(n_rec, sizeof(azh_access), &bytes) || __builtin_mul_overflow(c->n, n_times, &n_state))
+            return AZ_ERR_VALUE;
+        if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
+        if (!state) n_state = 0;
+        if (c->d_acc_out.cap < n_rec || c->d_pass_n.cap < c->n || c->d_acc_state.cap < n_state) HIP_TRY(hipStreamSynchronize(c->s_main));
+        if ((n_rec && c->d_acc_out.ensure(n_rec) != AZ_OK) || c->d_pass_n.ensure(c->n) != AZ_OK ||
+            (n_state && c->d_acc_state.ensure(n_state) != AZ_OK))
+            return AZ_ERR_HIP;
+        // (the first failure wins; the final sync always runs)
+        int32_t rc = find_access(c, times, n_times, offsets, target_index, false, nullptr, nullptr, grazing_alt_km, max_range_km,
+                                 n_rec ? c->d_acc_out.p : nullptr, max_windows, c->d_pass_n.p, n_state ? c->d_acc_state.p : nullptr, c->s_main);
+        auto back = [&](void *dst, const void *src, size_t nbytes) {
+            if (rc == AZ_OK && nbytes && !hip_ok(hipMemcpyAsync(dst, src, nbytes, hipMemcpyDeviceToHost, c->s_main), "D2H")) rc = AZ_ERR_HIP;
+        };
+        back(n_windows, c->d_pass_n.p, sizeof(uint32_t) * c->n);
+        back(out, c->d_acc_out.p, sizeof(azh_access) * n_rec);
+        back(state, c->d_acc_state.p, n_state);
         if (!hip_ok(hipStreamSynchronize(c->s_main), "sync") && rc == AZ_OK) rc = AZ_ERR_HIP;
         return rc;
     });

@@ -197,6 +197,31 @@ pub extern "c" fn azh_find_eclipses_device(h: ?*Handle, times_min: [*]const f64,
     reference_jd: f64, kind: i32, d_out: ?[*]Eclipse, max_eclipses: usize, d_n_eclipses: [*]u32, d_state_or_null: ?[*]u8,
     stream: ?*anyopaque) i32;
 
+// line of sight past a spherical Earth and access windows between a target and every member
+pub extern "c" fn azh_line_of_sight(r1: *const [3]f64, r2: *const [3]f64, grazing_alt_km: f64, clearance_km: ?*f64, range_km: ?*f64) i32; // 1 clear, 0 blocked
+pub const Access = extern struct {
+    t_start_min: f64,
+    t_end_min: f64,
+    min_range_km: f64,
+    flags: u32, // ACCESS_*
+    grid_start: u32,
+    grid_end: u32,
+    grid_min_range: u32,
+};
+pub const ACCESS_OPEN_AT_START: u32 = 1;
+pub const ACCESS_OPEN_AT_END: u32 = 2;
+pub const ACCESS_CUT_BY_ERROR: u32 = 4;
+pub const NO_TARGET: usize = ~@as(usize, 0); // exclude_index of azh_find_access_track_device: leave no member out
+pub extern "c" fn azh_find_access_host(h: ?*Handle, times_min: [*]const f64, n_times: usize, epoch_offsets_min: ?[*]const f64,
+    target_index: usize, grazing_alt_km: f64, max_range_km: f64, out: ?[*]Access, max_windows: usize, n_windows: [*]u32,
+    state_or_null: ?[*]u8) i32;
+pub extern "c" fn azh_find_access_device(h: ?*Handle, times_min: [*]const f64, n_times: usize, epoch_offsets_min: ?[*]const f64,
+    target_index: usize, grazing_alt_km: f64, max_range_km: f64, d_out: ?[*]Access, max_windows: usize, d_n_windows: [*]u32,
+    d_state_or_null: ?[*]u8, stream: ?*anyopaque) i32;
+pub extern "c" fn azh_find_access_track_device(h: ?*Handle, times_min: [*]const f64, n_times: usize, epoch_offsets_min: ?[*]const f64,
+    d_track_pos: [*]const f64, d_track_vel: [*]const f64, exclude_index: usize, grazing_alt_km: f64, max_range_km: f64,
+    d_out: ?[*]Access, max_windows: usize, d_n_windows: [*]u32, d_state_or_null: ?[*]u8, stream: ?*anyopaque) i32;
+
 // one process, several devices: replaces the std.Thread fan-out of Constellation.propagateConstellation
 // (src/Constellation.zig L557-603)
 pub const Group = opaque {};

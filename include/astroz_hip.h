@@ -344,6 +344,56 @@ int32_t azh_find_eclipses_device(azh_constellation *c, const double *times_min, 
                                  double reference_jd, int32_t kind, azh_eclipse *d_out, size_t max_eclipses,
                                  uint32_t *d_n_eclipses, uint8_t *d_state_or_null, void *stream);
 
+/* Line of sight between two TEME positions (km) past a spherical Earth of 6378.137 km raised by grazing_alt_km.  With
+ * d = r2 - r1 and tau = -r1.d / |d|^2, the clearance is the distance from the Earth's centre to the SEGMENT r1-r2:
+ * |r1 x r2| / |d| when 0 < tau < 1, else |r1| (tau <= 0 or |d| = 0) or |r2| (tau >= 1).  *clearance_km and *range_km (= |d|)
+ * are written when not NULL.  Returns 1 when the line is clear (clearance >= 6378.137 + grazing_alt_km), 0 when the Earth is in
+ * the way, -1 when a vector is NULL.  Oblateness, refraction and light time are not modelled.  Pure host function, the twin of
+ * the kernel's arithmetic. */
+int32_t azh_line_of_sight(const double r1[3], const double r2[3], double grazing_alt_km, double *clearance_km, double *range_km);
+
+/* Access windows (no reference counterpart): when every satellite of the handle has an unobstructed line to one target, within
+ * max_range_km, over the grid times_min (tsince as azh_propagate_*).  g = clearance - (6378.137 + grazing_alt_km), or the
+ * smaller of that and max_range_km - |d| with a finite max_range_km; access <=> g >= 0 and neither object has a propagation
+ * error at that grid point.
+ * The handle is propagated in AZ_OUT_TEME with velocities into the pass finders' device scratch (row windows of at most
+ * ~512 MiB) and a kernel scans each row against the target's track; starts / ends are the 0 -> 1 / 1 -> 0 transitions of the
+ * predicate.  Start and end times are the root of the cubic Hermite interpolant of g (values and rates at the two bracketing
+ * grid points) in that interval.  Nothing is propagated again.  A window shorter than the grid step that holds no grid point
+ * is not seen.  min_range_km / grid_min_range: the smallest |d| at a grid point inside the window and its index (the earliest
+ * among equal minima; not refined).
+ * The target: member target_index of the handle (_host, _device: its track is propagated into a buffer of the handle first),
+ * or an external track (_track_device: d_track_pos / d_track_vel = n_times x 3 doubles each, TEME km and km/s, on c's device;
+ * a point with a non-finite component counts as failed; exclude_index = a member to leave out, or (size_t)-1 for none).  The
+ * target's own row (the excluded member) reports no windows and a state row of 0.
+ * out: n_sats x max_windows records, the first max_windows windows of satellite s at out[s * max_windows ...], in time order;
+ * n_windows[s] = the TRUE number (may exceed max_windows); max_windows == 0 counts only; n_times == 0 zeroes the counts.
+ * state (may be NULL): n_sats x n_times bytes, satellite-major: 0 Earth in the way, 1 clear line but beyond max_range_km,
+ * 2 access, 255 where either object failed.
+ * AZ_ERR_VALUE, checked first and without touching the handle or a device: times_min not strictly increasing, grazing_alt_km
+ * not finite or < 0, max_range_km not a number or <= 0 (+infinity: no limit), max_windows > 0xffffffff; then, of the handle:
+ * target_index >= n_sats, exclude_index neither (size_t)-1 nor < n_sats.  AZ_ERR_NULL_POINTER as for azh_find_eclipses_*.
+ * _device / _track_device: out / n_windows / state on c's device, asynchronous on `stream` (NULL = the handle's). */
+typedef struct azh_access {
+    double t_start_min, t_end_min; /* on the caller's time axis (times_min), refined (above) */
+    double min_range_km;           /* smallest |d| at a grid point inside the window */
+    uint32_t flags;                /* AZH_ACCESS_* */
+    uint32_t grid_start, grid_end, grid_min_range; /* first / last grid index inside, index of min_range_km */
+} azh_access;
+#define AZH_ACCESS_OPEN_AT_START 1u /* in access at times_min[0]: start = first grid time, not refined */
+#define AZH_ACCESS_OPEN_AT_END 2u   /* still in access at the last grid time: end = last grid time, not refined */
+#define AZH_ACCESS_CUT_BY_ERROR 4u  /* begun or ended next to a grid point where either object failed: that end is the grid time */
+int32_t azh_find_access_host(azh_constellation *c, const double *times_min, size_t n_times, const double *epoch_offsets_min,
+                             size_t target_index, double grazing_alt_km, double max_range_km, azh_access *out, size_t max_windows,
+                             uint32_t *n_windows, uint8_t *state_or_null);
+int32_t azh_find_access_device(azh_constellation *c, const double *times_min, size_t n_times, const double *epoch_offsets_min,
+                               size_t target_index, double grazing_alt_km, double max_range_km, azh_access *d_out,
+                               size_t max_windows, uint32_t *d_n_windows, uint8_t *d_state_or_null, void *stream);
+int32_t azh_find_access_track_device(azh_constellation *c, const double *times_min, size_t n_times, const double *epoch_offsets_min,
+                                     const double *d_track_pos, const double *d_track_vel, size_t exclude_index,
+                                     double grazing_alt_km, double max_range_km, azh_access *d_out, size_t max_windows,
+                                     uint32_t *d_n_windows, uint8_t *d_state_or_null, void *stream);
+
 /* Fused single-target conjunction screen = Constellation.screenConstellation
  * (src/Constellation.zig L683-756; Python: Sgp4Constellation.screen_conjunction,
  * bindings/python/astroz/__init__.py L625-632).  For every satellite the minimum distance (km) to
