@@ -341,15 +341,8 @@ STATION_PASS_DTYPE = np.dtype([("station", "<u4")] + PASS_DTYPE.descr)
 _STATION_CALL_BYTES = 256 << 20
 
 
-def station_passes(source, times, stations, *, min_elevation=10.0, start_time=None, norad_id=None, fetch=None,
-                   allow_network=False):
-    """Passes of every satellite over each of several ground stations, from one propagation of the catalog.
-
-    ``stations``: a sequence of ``(lat_deg, lon_deg, alt_km)`` (geodetic WGS84); ``min_elevation``: degrees, a scalar or one
-    value per station; ``times`` as for ``passes()`` (strictly increasing).  Returns a numpy structured array, one row per
-    pass, sorted by (station, sat, rise): ``station`` (index into ``stations``) and the fields of ``passes()``.  Station st's
-    rows are the passes ``passes(source, times, stations[st], min_elevation=...)`` finds (times and angles equal to within
-    the last bits); the constellation's own observer is not changed."""
+def _stations_and_masks(stations, min_elevation):
+    """``stations`` as an (S, 3) float64 array and ``min_elevation`` as its (S,) masks, or ValueError."""
     try:
         st = np.array([[float(x) for x in s] for s in stations], dtype=np.float64)
     except (TypeError, ValueError):
@@ -366,9 +359,28 @@ def station_passes(source, times, stations, *, min_elevation=10.0, start_time=No
         raise ValueError("min_elevation must be a scalar or one value per station")
     if not np.isfinite(mask).all():
         raise ValueError("min_elevation must be finite")
+    return st, mask
+
+
+def _increasing_minutes(times):
+    """``times`` as a 1-D float64 array, strictly increasing, or ValueError."""
     minutes = np.ascontiguousarray(times, dtype=np.float64)
     if minutes.ndim != 1 or (len(minutes) > 1 and not (np.diff(minutes) > 0).all()):
         raise ValueError("times must be strictly increasing")
+    return minutes
+
+
+def station_passes(source, times, stations, *, min_elevation=10.0, start_time=None, norad_id=None, fetch=None,
+                   allow_network=False):
+    """Passes of every satellite over each of several ground stations, from one propagation of the catalog.
+
+    ``stations``: a sequence of ``(lat_deg, lon_deg, alt_km)`` (geodetic WGS84); ``min_elevation``: degrees, a scalar or one
+    value per station; ``times`` as for ``passes()`` (strictly increasing).  Returns a numpy structured array, one row per
+    pass, sorted by (station, sat, rise): ``station`` (index into ``stations``) and the fields of ``passes()``.  Station st's
+    rows are the passes ``passes(source, times, stations[st], min_elevation=...)`` finds (times and angles equal to within
+    the last bits); the constellation's own observer is not changed."""
+    st, mask = _stations_and_masks(stations, min_elevation)
+    minutes = _increasing_minutes(times)
     const = source if isinstance(source, Constellation) else Constellation(source, norad_id=norad_id, fetch=fetch,
                                                                            allow_network=allow_network)
     minutes, offsets, start = _minutes_and_offsets(const, minutes, start_time)
@@ -392,6 +404,80 @@ def station_passes(source, times, stations, *, min_elevation=10.0, start_time=No
         parts.append(out)
         lo += k
     return np.concatenate(parts) if parts else np.empty(0, dtype=STATION_PASS_DTYPE)
+
+
+# coverage(): one row per ground point
+COVERAGE_DTYPE = np.dtype([("covered_fraction", "<f8"), ("mean_in_view", "<f8"), ("min_in_view", "<u4"), ("max_in_view", "<u4"),
+                           ("n_gaps", "<u4"), ("max_gap", "<f8"), ("gap_start", "<f8"), ("gap_end", "<f8"), ("flags", "<u4")])
+# the counts matrix coverage() asks one C call for (the points are split over several calls beyond it; each repropagates)
+_COVERAGE_CALL_BYTES = 256 << 20
+
+
+def coverage(source, times, points, *, min_elevation=10.0, min_satellites=1, start_time=None, counts=False, norad_id=None,
+             fetch=None, allow_network=False):
+    """Ground coverage: how many satellites each of several ground points has in view at each of ``times``, and what that
+    means for the point over the whole grid.
+
+    ``points``: a sequence of ``(lat_deg, lon_deg, alt_km)`` (geodetic WGS84; ``grid_points()`` makes a lattice);
+    ``min_elevation``: degrees, a scalar or one value per point; ``times`` as for ``station_passes()`` (strictly increasing);
+    ``min_satellites``: the satellites in view from which a point counts as covered.  A satellite is in view at a grid time
+    when ``station_passes()`` has a pass of it over the point that holds that grid time: nothing is refined between grid
+    times.  Returns a numpy structured array, one row per point: ``covered_fraction`` (covered grid times / all grid times),
+    ``mean_in_view``, ``min_in_view``, ``max_in_view``, ``n_gaps`` (maximal runs of uncovered grid times), ``max_gap``
+    (minutes: the longest time the point can have been uncovered, from the last covered grid time before the gap to the
+    first after it, or to the ends of the grid), ``gap_start`` and ``gap_end`` (those two grid times, minutes) and ``flags``
+    (1: that gap is open at the first time, 2: at the last).  With ``counts=True`` also the ``(n_points, n_times)`` uint32
+    matrix of satellites in view.  The catalog is propagated and tested against every point on the GPU; only these come
+    back."""
+    pt, mask = _stations_and_masks(points, min_elevation)
+    minutes = _increasing_minutes(times)
+    k = _native._min_satellites(min_satellites)
+    const = source if isinstance(source, Constellation) else Constellation(source, norad_id=norad_id, fetch=fetch,
+                                                                           allow_network=allow_network)
+    minutes, offsets, start = _minutes_and_offsets(const, minutes, start_time)
+    n_t = len(minutes)
+    out = np.zeros(len(pt), dtype=COVERAGE_DTYPE)
+    matrix = np.zeros((len(pt), n_t), dtype=np.uint32) if counts else None
+    per_call = max(1, _COVERAGE_CALL_BYTES // max(1, 4 * n_t))  # points per call: their counts within _COVERAGE_CALL_BYTES
+    for lo in range(0, len(pt), per_call):
+        hi = min(len(pt), lo + per_call)
+        got = const._dev.coverage(minutes, offsets, pt[lo:hi], mask[lo:hi], reference_jd=start, min_satellites=k, counts=counts)
+        st = got[0] if counts else got
+        if counts:
+            matrix[lo:hi] = got[1]
+        o = out[lo:hi]
+        o["covered_fraction"] = st["n_covered"] / float(n_t) if n_t else 0.0
+        for f in ("mean_in_view", "min_in_view", "max_in_view", "n_gaps", "flags"):
+            o[f] = st[f]
+        o["max_gap"] = st["max_gap_min"]
+        if n_t:  # the grid times that bracket the gap (its own ends where it is open)
+            gap = st["n_gaps"] > 0
+            o["gap_start"] = np.where(gap, minutes[np.maximum(st["grid_gap_start"].astype(np.int64) - 1, 0)], 0.0)
+            o["gap_end"] = np.where(gap, minutes[np.minimum(st["grid_gap_end"].astype(np.int64) + 1, n_t - 1)], 0.0)
+    return (out, matrix) if counts else out
+
+
+def grid_points(lat_step_deg, lon_step_deg=None, *, lat_range=(-90, 90), alt_km=0.0):
+    """The cell centres of a latitude / longitude lattice as ``(P, 3)`` points ``(lat_deg, lon_deg, alt_km)`` for
+    ``coverage()``: cells of ``lat_step_deg`` x ``lon_step_deg`` (default: square) tile latitudes ``lat_range`` (clipped to
+    [-90, 90]; the last band is cut at its upper edge) and longitudes [-180, 180), latitude-major.  ``grid_points(5)`` is
+    the 36 x 72 global grid."""
+    dlat = float(lat_step_deg)
+    dlon = dlat if lon_step_deg is None else float(lon_step_deg)
+    if not (np.isfinite(dlat) and np.isfinite(dlon) and dlat > 0.0 and 0.0 < dlon <= 360.0):
+        raise ValueError("grid steps must be positive (the longitude step at most 360)")
+    lo, hi = max(-90.0, float(lat_range[0])), min(90.0, float(lat_range[1]))
+    if not lo < hi or not np.isfinite(float(alt_km)):
+        raise ValueError("lat_range must be (south, north) with south < north, alt_km finite")
+    edges = lo + dlat * np.arange(int(np.ceil((hi - lo) / dlat - 1e-9)) + 1)
+    lat = 0.5 * (edges[:-1] + np.minimum(edges[1:], hi))
+    lon = -180.0 + dlon * (np.arange(int(np.ceil(360.0 / dlon - 1e-9))) + 0.5)
+    lon = lon[lon < 180.0]
+    out = np.empty((len(lat), len(lon), 3))
+    out[..., 0] = lat[:, None]
+    out[..., 1] = lon[None, :]
+    out[..., 2] = float(alt_km)
+    return out.reshape(-1, 3)
 
 
 # eclipses(): one row per shadow interval
@@ -567,7 +653,7 @@ def escape_velocity(mu, radius):
     return _scalar(_native.lib().orbital_escape_velocity(float(mu), float(radius)), "orbital_escape_velocity", "invalid radius")
 
 
-__all__ = ["__version__", "Tle", "Sgp4Constellation", "Constellation", "propagate", "passes", "station_passes", "eclipses",
+__all__ = ["__version__", "Tle", "Sgp4Constellation", "Constellation", "propagate", "passes", "station_passes", "coverage", "grid_points", "COVERAGE_DTYPE", "eclipses",
            "sun_position", "ECLIPSE_DTYPE", "access", "ACCESS_DTYPE", "screen",
            "coarse_screen", "set_fetcher", "celestrak_url", "WGS72", "WGS84", "hohmann_transfer", "orbital_velocity", "orbital_period",
            "escape_velocity", "EARTH_MU", "EARTH_R_EQ", "EARTH_J2", "SUN_MU", "MOON_MU"]

@@ -32,6 +32,12 @@ ACCESS_DTYPE = np.dtype([("t_start_min", "<f8"), ("t_end_min", "<f8"), ("min_ran
                          ("grid_start", "<u4"), ("grid_end", "<u4"), ("grid_min_range", "<u4")])
 ACCESS_OPEN_AT_START, ACCESS_OPEN_AT_END, ACCESS_CUT_BY_ERROR = 1, 2, 4
 
+# azh_coverage and its flags
+COVERAGE_DTYPE = np.dtype([("mean_in_view", "<f8"), ("max_gap_min", "<f8"), ("n_covered", "<u4"), ("min_in_view", "<u4"),
+                           ("max_in_view", "<u4"), ("n_gaps", "<u4"), ("grid_gap_start", "<u4"), ("grid_gap_end", "<u4"),
+                           ("flags", "<u4"), ("reserved", "<u4")])
+COVERAGE_GAP_AT_START, COVERAGE_GAP_AT_END = 1, 2
+
 AZ_ERR_HIP = -200
 # azh_last_path bits (include/astroz_hip.h)
 PATH_ROWS_FAST, PATH_TILES_FAST, PATH_ROWS_GENERIC, PATH_LANE_SAT, PATH_DEEP_ROWS, PATH_QUASI_UNIFORM, PATH_COLS_FAST, PATH_HOST_STEP = 1, 2, 4, 8, 16, 32, 64, 128
@@ -57,6 +63,7 @@ EXPORTS = [
     "orbital_hohmann", "orbital_velocity", "orbital_period", "orbital_escape_velocity",
     "azh_coords_topocentric", "azh_set_observer", "azh_find_passes_host", "azh_find_passes_device",
     "azh_find_passes_stations_host", "azh_find_passes_stations_device",
+    "azh_coverage_host", "azh_coverage_device",
     "azh_sun_position_teme", "azh_selftest_sun", "azh_shadow_state", "azh_find_eclipses_host", "azh_find_eclipses_device",
     "azh_line_of_sight", "azh_find_access_host", "azh_find_access_device", "azh_find_access_track_device",
 ]
@@ -67,6 +74,13 @@ def _stations(stations, min_elevation_deg):
     st = np.ascontiguousarray(stations, dtype=np.float64).reshape(-1, 3)
     mk = np.ascontiguousarray(np.broadcast_to(np.asarray(min_elevation_deg, dtype=np.float64), (len(st),)))
     return st, mk
+
+
+def _min_satellites(k):
+    """min_satellites as the uint32 the C call takes: an integer >= 1."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 0xFFFFFFFF:
+        raise ValueError("min_satellites must be an integer >= 1")
+    return int(k)
 
 
 class NativeError(RuntimeError):
@@ -275,6 +289,10 @@ def lib():
     L.azh_find_passes_stations_host.restype = i32
     L.azh_find_passes_stations_device.argtypes = [vp, vp, sz, vp, dbl, vp, vp, sz, vp, sz, vp, vp]
     L.azh_find_passes_stations_device.restype = i32
+    L.azh_coverage_host.argtypes = [vp, vp, sz, vp, dbl, vp, vp, sz, u32, vp, vp]
+    L.azh_coverage_host.restype = i32
+    L.azh_coverage_device.argtypes = [vp, vp, sz, vp, dbl, vp, vp, sz, u32, vp, vp, vp]
+    L.azh_coverage_device.restype = i32
     L.azh_sun_position_teme.argtypes = [dbl, vp]
     L.azh_sun_position_teme.restype = None
     L.azh_selftest_sun.argtypes = [vp, sz, vp, i32]
@@ -549,6 +567,36 @@ class DeviceConstellation:
         check(lib().azh_find_passes_stations_device(self._h, times.ctypes.data, len(times), _ptr(off), float(reference_jd),
                                                     st.ctypes.data, mk.ctypes.data, len(st), d_out, int(max_passes), d_n_passes,
                                                     stream), "azh_find_passes_stations_device")
+
+    # -- ground coverage --------------------------------------------------------------------------
+    def coverage(self, times_min, offsets_min, points, min_elevation_deg, *, reference_jd=0.0, min_satellites=1, counts=False):
+        """Satellites in view over P ground points (azh_coverage_host): points (P, 3) (lat_deg, lon_deg, alt_km),
+        min_elevation_deg (P,) or a scalar -> stats (P,) of COVERAGE_DTYPE, and with counts=True also the (P, n_times) u32
+        matrix of satellites in view.  The handle's observer is neither needed nor changed."""
+        times = _f64(times_min)
+        off = None if offsets_min is None else _f64(offsets_min)
+        if off is not None and len(off) < self.n:
+            raise ValueError("epoch_offsets must have at least num_satellites elements")
+        pt, mk = _stations(points, min_elevation_deg)
+        stats = np.zeros(len(pt), dtype=COVERAGE_DTYPE)
+        cnt = np.zeros((len(pt), len(times)), dtype=np.uint32) if counts else None
+        check(lib().azh_coverage_host(self._h, times.ctypes.data, len(times), _ptr(off), float(reference_jd), pt.ctypes.data,
+                                      mk.ctypes.data, len(pt), _min_satellites(min_satellites), stats.ctypes.data,
+                                      None if cnt is None else cnt.ctypes.data), "azh_coverage_host")
+        return (stats, cnt) if counts else stats
+
+    def coverage_device(self, times_min, offsets_min, points, min_elevation_deg, d_stats, d_counts=None, *, reference_jd=0.0,
+                        min_satellites=1, stream=None):
+        """azh_coverage_device: d_stats / d_counts are raw device pointers (P records of COVERAGE_DTYPE, P x n_times u32 or
+        None for the statistics alone); asynchronous."""
+        times = _f64(times_min)
+        off = None if offsets_min is None else _f64(offsets_min)
+        if off is not None and len(off) < self.n:
+            raise ValueError("epoch_offsets must have at least num_satellites elements")
+        pt, mk = _stations(points, min_elevation_deg)
+        check(lib().azh_coverage_device(self._h, times.ctypes.data, len(times), _ptr(off), float(reference_jd), pt.ctypes.data,
+                                        mk.ctypes.data, len(pt), _min_satellites(min_satellites), d_stats, d_counts, stream),
+              "azh_coverage_device")
 
     # -- Earth shadow -----------------------------------------------------------------------------
     def find_eclipses(self, times_min, offsets_min=None, *, reference_jd, kind=SHADOW_UMBRA, max_eclipses=32, state=False):

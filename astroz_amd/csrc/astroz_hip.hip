@@ -25,6 +25,7 @@
 
 #include "kernels.h"
 #include "passes_kernel.h"
+#include "coverage_kernel.h"
 #include "sun.h"
 #include "eclipse_kernel.h"
 #include "los.h"
@@ -259,8 +260,10 @@ struct azh_constellation {
     DevBuf<unsigned char> d_pass_err;
     DevBuf<azh_pass> d_pass_out;          // ... and the records / counts of azh_find_passes_host
     DevBuf<uint32_t> d_pass_n;
-    std::vector<AzStation> h_stations;    // azh_find_passes_stations_*: the stations of the last call ...
+    std::vector<AzStation> h_stations;    // azh_find_passes_stations_* / azh_coverage_*: the stations (points) of the last call ...
     DevBuf<AzStation> d_stations;         // ... and their grow-only device copy
+    DevBuf<azh_coverage> d_cov_stats;     // azh_coverage_host: the records, and the counts of a call that asks for none
+    DevBuf<uint32_t> d_cov_counts;        // (azh_coverage_device with d_counts == NULL too)
     DevBuf<AzSunPoint> d_sun;             // azh_find_eclipses_*: the call's Sun table (one record per grid time) ...
     DevBuf<azh_eclipse> d_ecl_out;        // ... and the records / state matrix of azh_find_eclipses_host (counts: d_pass_n)
     DevBuf<unsigned char> d_ecl_state;
@@ -2551,24 +2554,24 @@ static bool times_increasing(const double *times, size_t n)
 
 // azh_find_passes_*: propagate to `mode` with rates, satellite-major, into the handle's scratch one row window at a time (at most
 // kPassScratch bytes: pos + vel + err), and scan every window's rows [lo, hi) with scan(lo, hi) behind its propagation.  With no
-// grid point the n_cnt counts are zeroed.
+// grid point the n_cnt counts are zeroed.  !with_vel: positions only (d_pass_vel is not touched), so a window holds twice the rows.
 static constexpr size_t kPassScratch = size_t(512) << 20;
 extern "C++" { // (templates)
 template <class Scan>
 static int32_t pass_windows(azh_constellation *c, const double *times, size_t n_times, const double *offsets, double reference_jd,
-                            int32_t mode, uint32_t *d_n, size_t n_cnt, hipStream_t st, Scan &&scan)
+                            int32_t mode, uint32_t *d_n, size_t n_cnt, hipStream_t st, Scan &&scan, bool with_vel = true)
 {
     if (n_times == 0) {
         HIP_TRY(hipMemsetAsync(d_n, 0, sizeof(uint32_t) * n_cnt, st));
         return AZ_OK;
     }
     if (int32_t rc = stage_inputs(c, times, n_times, offsets, nullptr, mode, reference_jd, st); rc != AZ_OK) return rc;
-    const size_t per_row = n_times * (6 * sizeof(double) + 1);
+    const size_t per_row = n_times * ((with_vel ? 6 : 3) * sizeof(double) + 1);
     const size_t rows_w = std::max<size_t>(1, std::min(c->n, kPassScratch / per_row));
-    const size_t words = rows_w * n_times * 3;
-    if (c->d_pass_pos.cap < words || c->d_pass_vel.cap < words || c->d_pass_err.cap < rows_w * n_times)
+    const size_t words = rows_w * n_times * 3, vel_words = with_vel ? words : 0;
+    if (c->d_pass_pos.cap < words || c->d_pass_vel.cap < vel_words || c->d_pass_err.cap < rows_w * n_times)
         HIP_TRY(hipStreamSynchronize(st)); // (launches in flight use the old buffers)
-    if (c->d_pass_pos.ensure(words) != AZ_OK || c->d_pass_vel.ensure(words) != AZ_OK || c->d_pass_err.ensure(rows_w * n_times) != AZ_OK)
+    if (c->d_pass_pos.ensure(words) != AZ_OK || c->d_pass_vel.ensure(vel_words) != AZ_OK || c->d_pass_err.ensure(rows_w * n_times) != AZ_OK)
         return AZ_ERR_HIP;
     for (size_t lo = 0; lo < c->n; lo += rows_w) {
         const size_t hi = std::min(c->n, lo + rows_w);
@@ -2577,8 +2580,8 @@ static int32_t pass_windows(azh_constellation *c, const double *times, size_t n_
         const uintptr_t pb = reinterpret_cast<uintptr_t>(c->d_pass_pos.p) - 3 * shift * sizeof(double);
         const uintptr_t vb = reinterpret_cast<uintptr_t>(c->d_pass_vel.p) - 3 * shift * sizeof(double);
         const uintptr_t eb = reinterpret_cast<uintptr_t>(c->d_pass_err.p) - shift;
-        if (int32_t rc = launch_all(c, reinterpret_cast<double *>(pb), reinterpret_cast<double *>(vb), AZ_LAYOUT_SAT_MAJOR, 0,
-                                    reinterpret_cast<uint8_t *>(eb), st, 0, lo, hi);
+        if (int32_t rc = launch_all(c, reinterpret_cast<double *>(pb), with_vel ? reinterpret_cast<double *>(vb) : nullptr,
+                                    AZ_LAYOUT_SAT_MAJOR, 0, reinterpret_cast<uint8_t *>(eb), st, 0, lo, hi);
             rc != AZ_OK)
             return rc;
         if (int32_t rc = scan(lo, hi); rc != AZ_OK) return rc;
@@ -2731,6 +2734,140 @@ int32_t azh_find_passes_stations_host(azh_constellation *c, const double *times,
     });
 }
 
+// ---- ground coverage -----------------------------------------------------------------------------------------------------
+// azh_coverage_*: Earth-fixed positions (no velocities) in the pass finders' scratch, k_coverage_count behind every window's
+// propagation into d_counts (zeroed first), k_coverage_stats behind the last.  The points travel as the stations do, padded to
+// whole point blocks with points that see nothing.
+static int32_t coverage(azh_constellation *c, const double *times, size_t n_times, const double *offsets, double reference_jd,
+                        const double *lla, const double *mask_deg, size_t n_pt, uint32_t min_sats, azh_coverage *d_stats,
+                        uint32_t *d_counts, hipStream_t st)
+{
+    if (n_times == 0) {
+        HIP_TRY(hipMemsetAsync(d_stats, 0, sizeof(azh_coverage) * n_pt, st));
+        return AZ_OK;
+    }
+    const size_t n_pb = (n_pt + AZ_COV_BLOCK_POINTS - 1) / AZ_COV_BLOCK_POINTS, n_pad = n_pb * AZ_COV_BLOCK_POINTS;
+    const size_t n_chunks = (n_times + 63) / 64;
+    if (!c->h_stations.empty() && c->d_stations.cap < n_pad) HIP_TRY(hipStreamSynchronize(st)); // (a scan in flight reads it)
+    if (c->d_stations.ensure(n_pad) != AZ_OK) return AZ_ERR_HIP;
+    c->h_stations.resize(n_pad);
+    for (size_t k = 0; k < n_pad; ++k) {
+        AzStation &S = c->h_stations[k];
+        if (k < n_pt) {
+            S.o = make_observer(lla[3 * k], lla[3 * k + 1], lla[3 * k + 2]);
+            S.min_el = mask_deg[k] * (AZ_PI / 180.0); // (find_passes_stations' arithmetic)
+            S.s2 = std::sin(S.min_el) * std::fabs(std::sin(S.min_el));
+        } else { // padding: U |U| <= |rho|^2 < 2 |rho|^2, and no elevation reaches the mask
+            S = AzStation{};
+            S.min_el = HUGE_VAL;
+            S.s2 = 2.0;
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(c->d_stations.p, c->h_stations.data(), sizeof(AzStation) * n_pad, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(d_counts, 0, sizeof(uint32_t) * n_pt * n_times, st));
+    // row slices: enough workgroups to fill the device when the points and chunks alone are few
+    const size_t cells = n_pb * n_chunks, want_blocks = 2048;
+    int32_t rc = pass_windows(
+        c, times, n_times, offsets, reference_jd, AZ_OUT_ECEF, nullptr, 0, st,
+        [&](size_t lo, size_t hi) -> int32_t {
+            const size_t tiles = (hi - lo + AZ_COV_TILE - 1) / AZ_COV_TILE;
+            const size_t slices = std::max<size_t>(1, std::min<size_t>({tiles, (want_blocks + cells - 1) / cells, 65535}));
+            CoverageCountArgs q{};
+            q.pos = c->d_pass_pos.p; q.err = c->d_pass_err.p;
+            q.n_times = (unsigned)n_times; q.n_rows = (unsigned)(hi - lo);
+            q.slice_rows = (unsigned)((tiles + slices - 1) / slices * AZ_COV_TILE);
+            q.pt = c->d_stations.p; q.n_points = (unsigned)n_pt; q.n_point_blocks = (unsigned)n_pb;
+            q.counts = d_counts;
+            const unsigned gz = (unsigned)((q.n_rows + q.slice_rows - 1) / q.slice_rows);
+            hipLaunchKernelGGL(k_coverage_count, dim3((unsigned)cells, 1, gz), dim3(64 * AZ_COV_WAVES), 0, st, q);
+            HIP_TRY(hipGetLastError());
+            return AZ_OK;
+        },
+        false);
+    if (rc != AZ_OK) return rc;
+    CoverageStatsArgs q{};
+    q.counts = d_counts; q.times = c->d_times.p; q.n_times = (unsigned)n_times; q.n_points = (unsigned)n_pt;
+    q.min_satellites = min_sats; q.out = d_stats;
+    hipLaunchKernelGGL(k_coverage_stats, dim3((unsigned)((n_pt + AZ_COV_STAT_WAVES - 1) / AZ_COV_STAT_WAVES)), dim3(64 * AZ_COV_STAT_WAVES), 0,
+                       st, q);
+    HIP_TRY(hipGetLastError());
+    return AZ_OK;
+}
+
+static constexpr size_t kCoverageMaxBlocks = size_t(1) << 22;
+// the argument rules of both variants, checked before the device is touched; n_cells = n_points x n_times
+static int32_t coverage_args(const double *times, size_t n_times, const double *lla, const double *mask_deg, size_t n_pt,
+                             uint32_t min_sats, size_t &n_cells)
+{
+    size_t bytes;
+    if (min_sats == 0 || n_pt > 0xffffffffu || n_times > 0xffffffffu || __builtin_mul_overflow(n_pt, n_times, &n_cells) ||
+        __builtin_mul_overflow(n_cells, sizeof(uint32_t), &bytes) || __builtin_mul_overflow(n_pt, sizeof(azh_coverage), &bytes))
+        return AZ_ERR_VALUE;
+    // the counting launch: one workgroup of 64 AZ_COV_WAVES threads per (point block, chunk of 64 times) and row slice -- rows
+    // are sliced only while there are fewer than ~2,048 of these -- within the 2^32 threads of a launch
+    const size_t n_pb = (n_pt + AZ_COV_BLOCK_POINTS - 1) / AZ_COV_BLOCK_POINTS, n_chunks = (n_times + 63) / 64;
+    if (n_pb * n_chunks > kCoverageMaxBlocks) return AZ_ERR_VALUE;
+    for (size_t k = 0; k < n_pt; ++k)
+        if (!observer_ok(lla[3 * k], lla[3 * k + 1], lla[3 * k + 2]) || !std::isfinite(mask_deg[k])) return AZ_ERR_VALUE;
+    return times_increasing(times, n_times) ? AZ_OK : AZ_ERR_VALUE;
+}
+
+// the counts of a call that asks for none: the handle's grow-only buffer
+static int32_t coverage_counts(azh_constellation *c, size_t n_cells, hipStream_t st, uint32_t *&d_counts)
+{
+    if (d_counts || n_cells == 0) return AZ_OK;
+    if (c->d_cov_counts.cap < n_cells) HIP_TRY(hipStreamSynchronize(st)); // (a call in flight uses the old buffer)
+    if (c->d_cov_counts.ensure(n_cells) != AZ_OK) return AZ_ERR_HIP;
+    d_counts = c->d_cov_counts.p;
+    return AZ_OK;
+}
+
+int32_t azh_coverage_device(azh_constellation *c, const double *times, size_t n_times, const double *offsets, double reference_jd,
+                            const double *points_lla, const double *min_elevation_deg, size_t n_points, uint32_t min_satellites,
+                            azh_coverage *d_stats, uint32_t *d_counts, void *stream)
+{
+    return guarded([&]() -> int32_t {
+        if (!c || (n_times && !times) || (n_points && (!points_lla || !min_elevation_deg || !d_stats))) return AZ_ERR_NULL_POINTER;
+        size_t n_cells = 0;
+        if (int32_t rc = coverage_args(times, n_times, points_lla, min_elevation_deg, n_points, min_satellites, n_cells); rc != AZ_OK)
+            return rc;
+        if (n_points == 0) return AZ_OK;
+        if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
+        hipStream_t st = stream ? (hipStream_t)stream : c->s_main;
+        if (int32_t rc = coverage_counts(c, n_cells, st, d_counts); rc != AZ_OK) return rc;
+        return coverage(c, times, n_times, offsets, reference_jd, points_lla, min_elevation_deg, n_points, min_satellites, d_stats,
+                        d_counts, st);
+    });
+}
+
+int32_t azh_coverage_host(azh_constellation *c, const double *times, size_t n_times, const double *offsets, double reference_jd,
+                          const double *points_lla, const double *min_elevation_deg, size_t n_points, uint32_t min_satellites,
+                          azh_coverage *stats, uint32_t *counts)
+{
+    return guarded([&]() -> int32_t {
+        if (!c || (n_times && !times) || (n_points && (!points_lla || !min_elevation_deg || !stats))) return AZ_ERR_NULL_POINTER;
+        size_t n_cells = 0;
+        if (int32_t rc = coverage_args(times, n_times, points_lla, min_elevation_deg, n_points, min_satellites, n_cells); rc != AZ_OK)
+            return rc;
+        if (n_points == 0) return AZ_OK;
+        if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
+        if (c->d_cov_stats.cap < n_points) HIP_TRY(hipStreamSynchronize(c->s_main));
+        if (c->d_cov_stats.ensure(n_points) != AZ_OK) return AZ_ERR_HIP;
+        uint32_t *d_counts = nullptr;
+        if (int32_t rc = coverage_counts(c, n_cells, c->s_main, d_counts); rc != AZ_OK) return rc;
+        // (the first failure wins; the final sync always runs)
+        int32_t rc = coverage(c, times, n_times, offsets, reference_jd, points_lla, min_elevation_deg, n_points, min_satellites,
+                              c->d_cov_stats.p, d_counts, c->s_main);
+        auto back = [&](void *dst, const void *src, size_t nbytes) {
+            if (rc == AZ_OK && nbytes && !hip_ok(hipMemcpyAsync(dst, src, nbytes, hipMemcpyDeviceToHost, c->s_main), "D2H")) rc = AZ_ERR_HIP;
+        };
+        back(stats, c->d_cov_stats.p, sizeof(azh_coverage) * n_points);
+        if (counts) back(counts, d_counts, sizeof(uint32_t) * n_cells);
+        if (!hip_ok(hipStreamSynchronize(c->s_main), "sync") && rc == AZ_OK) rc = AZ_ERR_HIP;
+        return rc;
+    });
+}
+
 // ---- the Sun, the Earth's shadow, eclipse intervals ----------------------------------------------------------------------
 void azh_sun_position_teme(double jd, double sun_km[3])
 {
@@ -2822,6 +2959,8 @@ int32_t azh_find_eclipses_host(azh_constellation *c, const double *times, size_t
         if ((n_rec && c->d_ecl_out.ensure(n_rec) != AZ_OK) || c->d_pass_n.ensure(c->n) != AZ_OK ||
             (n_state && c->d_ecl_state.ensure(n_state) != AZ_OK))
             return AZ_ERR_HIP;
+        // (k_eclipses writes the slots it fills and the whole buffer goes back: the others are zeros, not what the allocation held)
+        if (n_rec) HIP_TRY(hipMemsetAsync(c->d_ecl_out.p, 0, sizeof(azh_eclipse) * n_rec, c->s_main));
         // (the first failure wins; the final sync always runs)
         int32_t rc = find_eclipses(c, times, n_times, offsets, reference_jd, kind, n_rec ? c->d_ecl_out.p : nullptr, max_eclipses,
                                    c->d_pass_n.p, n_state ? c->d_ecl_state.p : nullptr, c->s_main);

@@ -358,6 +358,26 @@ struct AzStation {
     double s2;     // sin(min_el) |sin(min_el)|
 };
 
+// The up decision of an Earth-fixed position R seen from station S, the one every kernel that asks "in view?" takes: the
+// cheap test above, d = U |U| - s |s| |rho|^2 against a margin of 1e-12 |rho|^2.  Below the margin the position is down and
+// el is left alone.  Above it the position is up without more when the caller has no use for the elevation (!WANT_EL);
+// otherwise -- inside the margin always -- el is the exact elevation (az_topocentric's) and el >= min_el decides.
+template <bool WANT_EL>
+__device__ __forceinline__ bool az_station_up(const double R[3], const AzStation &S, double &el)
+{
+    const double dx = R[0] - S.o.x, dy = R[1] - S.o.y, dz = R[2] - S.o.z;
+    const double q = fma(S.o.cos_lon, dx, S.o.sin_lon * dy);
+    const double U = fma(S.o.cos_lat, q, S.o.sin_lat * dz);
+    const double rho2 = fma(dx, dx, fma(dy, dy, dz * dz));
+    const double d = fma(U, fabs(U), -(S.s2 * rho2)), margin = 1.0e-12 * rho2;
+    if (!(d >= -margin)) return false;
+    if (!WANT_EL && d > margin) return true;
+    double a[3] = {R[0], R[1], R[2]}, ad[3] = {0.0, 0.0, 0.0}; // (the position slot does not read the velocity)
+    az_topocentric<true>(a, ad, S.o);
+    el = a[1];
+    return el >= S.min_el;
+}
+
 #define AZ_STATION_GROUP 64
 struct StationPassArgs {
     const double *pos, *vel;  // [row - row0][n_times][3]: ECEF position, rotated velocity
@@ -428,20 +448,9 @@ __global__ void __launch_bounds__(64 * AZ_PASS_WAVES) k_passes_stations(StationP
         for (unsigned j = 0; j < p.n_st; ++j) {
             const AzStation S = p.st[j]; // (wave-uniform)
             bool in_pass = (in_pass_mask >> j) & 1u;
-            // the cheap test: U |U| against s |s| |rho|^2, exact elevation near the mask
-            const double dx = R[0] - S.o.x, dy = R[1] - S.o.y, dz = R[2] - S.o.z;
-            const double q = fma(S.o.cos_lon, dx, S.o.sin_lon * dy);
-            const double U = fma(S.o.cos_lat, q, S.o.sin_lat * dz);
-            const double rho2 = fma(dx, dx, fma(dy, dy, dz * dz));
-            const double d = fma(U, fabs(U), -(S.s2 * rho2)), margin = 1.0e-12 * rho2;
-            if (!in_pass && !az_any(ok && d >= -margin)) continue; // nothing up, nothing under way
+            // (a chunk with nothing up and no pass under way costs the cheap test only; the elevation is read on up lanes only)
             double el = 0.0;
-            if (ok) {
-                double a[3] = {R[0], R[1], R[2]}, ad[3] = {0.0, 0.0, 0.0}; // (the position slot does not read the velocity)
-                az_topocentric<true>(a, ad, S.o);
-                el = a[1];
-            }
-            const uint64_t m = __ballot(ok && el >= S.min_el);
+            const uint64_t m = __ballot(ok && az_station_up<true>(R, S, el));
             if (!in_pass && m == 0) continue;
 
             AzPassState u = az_state_of(mine, j);

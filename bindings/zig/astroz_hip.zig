@@ -174,6 +174,28 @@ pub extern "c" fn azh_find_passes_stations_device(h: ?*Handle, times_min: [*]con
     epoch_offsets_min: ?[*]const f64, reference_jd: f64, stations_lla: [*]const [3]f64, min_elevation_deg: [*]const f64,
     n_stations: usize, d_out: [*]Pass, max_passes: usize, d_n_passes: [*]u32, stream: ?*anyopaque) i32;
 
+// ground coverage: satellites in view per (ground point, grid time) and the statistics of every point's series
+pub const Coverage = extern struct {
+    mean_in_view: f64,
+    max_gap_min: f64,
+    n_covered: u32,
+    min_in_view: u32,
+    max_in_view: u32,
+    n_gaps: u32,
+    grid_gap_start: u32,
+    grid_gap_end: u32,
+    flags: u32,
+    reserved: u32,
+};
+pub const COVERAGE_GAP_AT_START: u32 = 1;
+pub const COVERAGE_GAP_AT_END: u32 = 2;
+pub extern "c" fn azh_coverage_host(h: ?*Handle, times_min: [*]const f64, n_times: usize, epoch_offsets_min: ?[*]const f64,
+    reference_jd: f64, points_lla: [*]const [3]f64, min_elevation_deg: [*]const f64, n_points: usize, min_satellites: u32,
+    stats: [*]Coverage, counts_or_null: ?[*]u32) i32;
+pub extern "c" fn azh_coverage_device(h: ?*Handle, times_min: [*]const f64, n_times: usize, epoch_offsets_min: ?[*]const f64,
+    reference_jd: f64, points_lla: [*]const [3]f64, min_elevation_deg: [*]const f64, n_points: usize, min_satellites: u32,
+    d_stats: [*]Coverage, d_counts_or_null: ?[*]u32, stream: ?*anyopaque) i32;
+
 // the Sun, the Earth's shadow and eclipse intervals
 pub extern "c" fn azh_sun_position_teme(jd: f64, sun_km: *[3]f64) void; // Almanac low-precision series (Vallado, "Sun"), km
 pub extern "c" fn azh_selftest_sun(jd: [*]const f64, n: usize, out3n: [*]f64, device: i32) i32; // the device twin (KAT)

@@ -297,6 +297,41 @@ int32_t azh_find_passes_stations_device(azh_constellation *c, const double *time
                                         const double *min_elevation_deg, size_t n_stations, azh_pass *d_out, size_t max_passes,
                                         uint32_t *d_n_passes, void *stream);
 
+/* Ground coverage (no reference counterpart): for each of n_points ground points and each grid time, the number of satellites
+ * in view, and per point the statistics of that series.  times_min, epoch_offsets_min, reference_jd, tsince and GMST as
+ * azh_find_passes_stations_*; points_lla: n_points x 3 (lat_deg, lon_deg, alt_km), geodetic WGS84, validated like stations;
+ * min_elevation_deg: n_points masks (degrees, finite); min_satellites >= 1: the satellites in view from which a point counts
+ * as covered.  Host arrays in both variants.  An invalid point, mask or time axis, min_satellites == 0, an n_points x
+ * n_times that overflows, or more than 2^22 blocks of (32 points x 64 grid times) -> AZ_ERR_VALUE before any device work,
+ * nothing written; n_points == 0 -> AZ_OK, nothing done.
+ * Satellite s is in view of point p at grid index i when its propagation there did not fail and the up decision of
+ * azh_find_passes_stations_* holds for its Earth-fixed position: counts[p * n_times + i] is 1 for every pass record that
+ * call would write with grid_rise <= i <= grid_set.  The handle is propagated once per row window in AZ_OUT_ECEF without
+ * velocities; nothing is refined between grid times.  counts (may be NULL: statistics only): n_points x n_times.
+ * stats: one record per point, with covered(i) := counts[p][i] >= min_satellites.  A gap is a maximal run [a, b] of
+ * uncovered grid indices; its length is times[min(b + 1, n_times - 1)] - times[max(a - 1, 0)], the longest time the point
+ * can have been uncovered.  n_times == 0: the records are zeroed and no counts are written.
+ * The handle's own observer is neither needed nor changed.  _device: stats / counts on c's device, asynchronous on
+ * `stream` (NULL = the handle's). */
+typedef struct azh_coverage {
+    double mean_in_view;                     /* sum of the point's counts / n_times */
+    double max_gap_min;                      /* length of the longest gap (minutes); 0 without a gap */
+    uint32_t n_covered;                      /* covered grid times */
+    uint32_t min_in_view, max_in_view;       /* extremes of the counts over the grid */
+    uint32_t n_gaps;
+    uint32_t grid_gap_start, grid_gap_end;   /* a and b of the longest gap (the earliest on ties); 0 without a gap */
+    uint32_t flags;                          /* AZH_COVERAGE_* of the longest gap */
+    uint32_t reserved;                       /* 0 */
+} azh_coverage;
+#define AZH_COVERAGE_GAP_AT_START 1u /* the longest gap is open at times_min[0] */
+#define AZH_COVERAGE_GAP_AT_END 2u   /* the longest gap is open at the last grid time */
+int32_t azh_coverage_host(azh_constellation *c, const double *times_min, size_t n_times, const double *epoch_offsets_min,
+                          double reference_jd, const double *points_lla, const double *min_elevation_deg, size_t n_points,
+                          uint32_t min_satellites, azh_coverage *stats, uint32_t *counts_or_null);
+int32_t azh_coverage_device(azh_constellation *c, const double *times_min, size_t n_times, const double *epoch_offsets_min,
+                            double reference_jd, const double *points_lla, const double *min_elevation_deg, size_t n_points,
+                            uint32_t min_satellites, azh_coverage *d_stats, uint32_t *d_counts_or_null, void *stream);
+
 /* The Sun's position (no reference counterpart): the low-precision series of the Astronomical Almanac as Vallado gives it
  * (algorithm "Sun"; 0.01 degrees, 1950-2050), km, for the Julian date jd.  jd is taken as UTC (UT1 and TT are not told apart)
  * and the mean-of-date vector is used as TEME; both are below the series' own 0.01 degrees.  Pure host function: the twin of
