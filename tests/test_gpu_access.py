@@ -157,9 +157,9 @@ def grid_state(P, bad, TP, h, max_range):
     return st, ~bad & (np.minimum(np.abs(gc), np.abs(gr)) < 1e-9)
 
 
-def check_against_scan(native, dev, off, times, target, h, max_range, room=ROOM):
+def check_against_scan(native, dev, off, times, target, h, max_range, room=ROOM, collect=None):
     """One call of the finder against the numpy scan of propagate_host's TEME output; returns (records, counts, state,
-    windows, worst |dt| min, grid points too close to call)."""
+    windows, worst |dt| min, grid points too close to call).  collect: a list that receives every row's scan."""
     n, nt = dev.n, len(times)
     P, V = np.empty((n, nt, 3)), np.empty((n, nt, 3))
     E = np.zeros((n, nt), dtype=np.uint8)
@@ -175,6 +175,8 @@ def check_against_scan(native, dev, off, times, target, h, max_range, room=ROOM)
         want = [] if s == target else scan_access(times, P[s], V[s], bad[s], P[target], V[target], h, max_range)
         assert cnt[s] == len(want), (s, int(cnt[s]), len(want))
         total += len(want)
+        if collect is not None:
+            collect.append(want)
         for k, w in enumerate(want[:room]):
             g = rec[s, k]
             for f in ("flags", "grid_start", "grid_end", "grid_min_range"):
