@@ -577,6 +577,53 @@ def access(source, times, target, *, grazing_altitude=0.0, max_range=None, start
     return (out, res[2]) if state else out
 
 
+# conjunctions(): one row per refined close approach
+CONJUNCTION_DTYPE = np.dtype([("target", "<u4"), ("sat", "<u4"), ("tca", "<f8"), ("miss", "<f8"), ("rel_speed", "<f8"),
+                              ("grid_index", "<u4")])
+_CONJUNCTION_ROOM = 4096  # records the first call of conjunctions() has room for
+
+
+def conjunctions(source, times, targets, threshold=10.0, *, start_time=None, norad_id=None, fetch=None, allow_network=False):
+    """Refined close approaches between the satellites ``targets`` (an output row or a sequence of them, as for ``screen()``;
+    repeats allowed) and every other satellite during ``times`` (minutes from ``start_time``, default now; strictly
+    increasing): every approach whose miss distance is below ``threshold`` km.
+
+    Returns a numpy structured array, one row per approach, sorted by (target, sat, tca): ``target`` and ``sat`` (output
+    rows), ``tca`` (minutes from ``start_time``), ``miss`` (km) and ``rel_speed`` (km/s) at the closest approach, and
+    ``grid_index`` (the grid interval ``[grid_index, grid_index + 1]`` that holds it).  An approach is looked for in every grid
+    interval at whose left end the two close in and at whose right end they no longer do; inside it the relative track is the
+    cubic Hermite interpolant of the propagated states, so the answer sees between grid points (unlike ``screen()``, which
+    reports distances AT grid times).  Not reported: a minimum at the first or last time, next to a failed propagation of
+    either satellite, or in an interval that also holds a maximum.  No light time, covariance or collision probability.  The
+    propagation and the search run on the GPU; only the records come back."""
+    try:
+        rows = np.atleast_1d(np.asarray(targets))
+        ok = rows.ndim == 1 and rows.size > 0 and rows.dtype != np.bool_ and np.issubdtype(rows.dtype, np.integer) and not (rows < 0).any()
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("targets must be a satellite index or a non-empty sequence of them")
+    thr = float(threshold)
+    if not (np.isfinite(thr) and thr > 0.0):
+        raise ValueError("threshold must be finite and > 0 km")
+    minutes = np.ascontiguousarray(times, dtype=np.float64)
+    if minutes.ndim != 1 or (len(minutes) > 1 and not (np.diff(minutes) > 0).all()):
+        raise ValueError("times must be strictly increasing")
+    const = source if isinstance(source, Constellation) else Constellation(source, norad_id=norad_id, fetch=fetch,
+                                                                           allow_network=allow_network)
+    if int(rows.max()) >= const.num_satellites:
+        raise ValueError("target index out of range")
+    minutes, offsets, start = _minutes_and_offsets(const, minutes, start_time)
+    find = lambda room: const._dev.find_conjunctions(minutes, rows, thr, offsets, max_events=room)  # noqa: E731
+    rec, n_ev = find(_CONJUNCTION_ROOM)
+    if n_ev > len(rec):  # more events than room: once more with room for all of them
+        rec, n_ev = find(n_ev)
+    out = np.empty(len(rec), dtype=CONJUNCTION_DTYPE)
+    out["target"], out["sat"], out["grid_index"] = rows[rec["target"]], rec["sat"], rec["grid_index"]
+    out["tca"], out["miss"], out["rel_speed"] = rec["t_tca_min"], rec["miss_km"], rec["rel_speed_km_s"]
+    return out[np.lexsort((out["tca"], out["sat"], out["target"]))]  # (slots of the same row interleave)
+
+
 def screen(source, times, threshold=10.0, *, target=None, start_time=None, norad_id=None, fetch=None, allow_network=False):
     """Screen a constellation for conjunction events (reference __init__.py L535-658).
 
@@ -654,7 +701,7 @@ def escape_velocity(mu, radius):
 
 
 __all__ = ["__version__", "Tle", "Sgp4Constellation", "Constellation", "propagate", "passes", "station_passes", "coverage", "grid_points", "COVERAGE_DTYPE", "eclipses",
-           "sun_position", "ECLIPSE_DTYPE", "access", "ACCESS_DTYPE", "screen",
+           "sun_position", "ECLIPSE_DTYPE", "access", "ACCESS_DTYPE", "conjunctions", "CONJUNCTION_DTYPE", "screen",
            "coarse_screen", "set_fetcher", "celestrak_url", "WGS72", "WGS84", "hohmann_transfer", "orbital_velocity", "orbital_period",
            "escape_velocity", "EARTH_MU", "EARTH_R_EQ", "EARTH_J2", "SUN_MU", "MOON_MU"]
 # (the reference's package also re-exports bi_elliptic_transfer, lambert and propagate_numerical -- its orbital-mechanics and

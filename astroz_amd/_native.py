@@ -31,6 +31,9 @@ SHADOW_KINDS = {"umbra": SHADOW_UMBRA, "penumbra": SHADOW_PENUMBRA}
 ACCESS_DTYPE = np.dtype([("t_start_min", "<f8"), ("t_end_min", "<f8"), ("min_range_km", "<f8"), ("flags", "<u4"),
                          ("grid_start", "<u4"), ("grid_end", "<u4"), ("grid_min_range", "<u4")])
 ACCESS_OPEN_AT_START, ACCESS_OPEN_AT_END, ACCESS_CUT_BY_ERROR = 1, 2, 4
+# azh_conjunction
+CONJUNCTION_DTYPE = np.dtype([("t_tca_min", "<f8"), ("miss_km", "<f8"), ("rel_speed_km_s", "<f8"), ("target", "<u4"),
+                              ("sat", "<u4"), ("grid_index", "<u4"), ("reserved", "<u4")])
 
 # azh_coverage and its flags
 COVERAGE_DTYPE = np.dtype([("mean_in_view", "<f8"), ("max_gap_min", "<f8"), ("n_covered", "<u4"), ("min_in_view", "<u4"),
@@ -66,6 +69,7 @@ EXPORTS = [
     "azh_coverage_host", "azh_coverage_device",
     "azh_sun_position_teme", "azh_selftest_sun", "azh_shadow_state", "azh_find_eclipses_host", "azh_find_eclipses_device",
     "azh_line_of_sight", "azh_find_access_host", "azh_find_access_device", "azh_find_access_track_device",
+    "azh_closest_approach", "azh_find_conjunctions_host", "azh_find_conjunctions_device",
 ]
 
 
@@ -74,6 +78,14 @@ def _stations(stations, min_elevation_deg):
     st = np.ascontiguousarray(stations, dtype=np.float64).reshape(-1, 3)
     mk = np.ascontiguousarray(np.broadcast_to(np.asarray(min_elevation_deg, dtype=np.float64), (len(st),)))
     return st, mk
+
+
+def _targets(targets):
+    """Target rows as the contiguous size_t array the C call takes: a non-empty sequence of integers >= 0 (or one integer)."""
+    a = np.atleast_1d(np.asarray(targets))
+    if a.ndim != 1 or a.size == 0 or a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer) or (a < 0).any():
+        raise ValueError("targets must be a satellite index or a non-empty sequence of them")
+    return np.ascontiguousarray(a, dtype=np.uintp)
 
 
 def _min_satellites(k):
@@ -311,6 +323,12 @@ def lib():
     L.azh_find_access_device.restype = i32
     L.azh_find_access_track_device.argtypes = [vp, vp, sz, vp, vp, vp, sz, dbl, dbl, vp, sz, vp, vp, vp]
     L.azh_find_access_track_device.restype = i32
+    L.azh_closest_approach.argtypes = [vp, vp, vp, vp, dbl, vp, vp, vp]
+    L.azh_closest_approach.restype = i32
+    L.azh_find_conjunctions_host.argtypes = [vp, vp, sz, vp, vp, sz, dbl, vp, sz, vp]
+    L.azh_find_conjunctions_host.restype = i32
+    L.azh_find_conjunctions_device.argtypes = [vp, vp, sz, vp, vp, sz, dbl, vp, sz, vp, vp]
+    L.azh_find_conjunctions_device.restype = i32
     L.orbital_hohmann.argtypes = [dbl, dbl, dbl, vp]
     L.orbital_hohmann.restype = i32
     for f, n in (("orbital_velocity", 3), ("orbital_period", 2), ("orbital_escape_velocity", 2)):
@@ -664,6 +682,33 @@ class DeviceConstellation:
         check(lib().azh_find_access_track_device(self._h, times.ctypes.data, len(times), _ptr(off), d_track_pos, d_track_vel, ex,
                                                  float(grazing_alt_km), _max_range(max_range_km), d_out, int(max_windows),
                                                  d_n_windows, d_state, stream), "azh_find_access_track_device")
+
+    # -- refined close approaches ----------------------------------------------------------------
+    def find_conjunctions(self, times_min, targets, threshold_km, offsets_min=None, *, max_events=65536):
+        """Close approaches of every member to the members `targets` below threshold_km (azh_find_conjunctions_host):
+        (records of CONJUNCTION_DTYPE, the min(n_events, max_events) stored ones sorted by (target slot, sat, t_tca_min);
+        n_events, the TRUE number, which may exceed max_events)."""
+        times = _f64(times_min)
+        off = None if offsets_min is None else _f64(offsets_min)
+        if off is not None and len(off) < self.n:
+            raise ValueError("epoch_offsets must have at least num_satellites elements")
+        tg = _targets(targets)
+        out = np.zeros(int(max_events), dtype=CONJUNCTION_DTYPE)
+        cnt = np.zeros(1, dtype=np.uint32)
+        check(lib().azh_find_conjunctions_host(self._h, times.ctypes.data, len(times), _ptr(off), tg.ctypes.data, len(tg),
+                                               float(threshold_km), out.ctypes.data if max_events else None, int(max_events),
+                                               cnt.ctypes.data), "azh_find_conjunctions_host")
+        return out[:min(int(cnt[0]), int(max_events))], int(cnt[0])
+
+    def find_conjunctions_device(self, times_min, targets, threshold_km, offsets_min, d_out, max_events, d_n_events, *, stream=None):
+        """azh_find_conjunctions_device: d_out / d_n_events are raw device pointers (max_events records of CONJUNCTION_DTYPE,
+        one u32); asynchronous.  The order of the records is unspecified."""
+        times = _f64(times_min)
+        off = None if offsets_min is None else _f64(offsets_min)
+        tg = _targets(targets)
+        check(lib().azh_find_conjunctions_device(self._h, times.ctypes.data, len(times), _ptr(off), tg.ctypes.data, len(tg),
+                                                 float(threshold_km), d_out, int(max_events), d_n_events, stream),
+              "azh_find_conjunctions_device")
 
     def screen_all(self, times_min, threshold=10.0, offsets_min=None, max_results=10_000_000):
         """All-vs-all: propagate on the device and screen there: (pairs (k,2) u32, t_index (k,) u32),
@@ -1055,6 +1100,21 @@ def line_of_sight(r1, r2, grazing_alt_km=0.0):
     cl, rg = C.c_double(), C.c_double()
     ok = lib().azh_line_of_sight(a.ctypes.data, b.ctypes.data, float(grazing_alt_km), C.addressof(cl), C.addressof(rg))
     return bool(ok), cl.value, rg.value
+
+
+def closest_approach(d0, w0, d1, w1, dt_min):
+    """The closest approach inside one grid interval of dt_min minutes (azh_closest_approach): relative positions d0, d1 (km)
+    and velocities w0, w1 (km/s) at its ends.  (sigma, miss km, relative speed km/s) on a bracket -- d0.w0 < 0 <= d1.w1 --
+    and None otherwise."""
+    a, b, c, d = _f64(d0), _f64(w0), _f64(d1), _f64(w1)
+    if not (len(a) == len(b) == len(c) == len(d) == 3):
+        raise ValueError("d0, w0, d1, w1 must be 3-vectors")
+    s, m, v = C.c_double(), C.c_double(), C.c_double()
+    rc = lib().azh_closest_approach(a.ctypes.data, b.ctypes.data, c.ctypes.data, d.ctypes.data, float(dt_min), C.addressof(s),
+                                    C.addressof(m), C.addressof(v))
+    if rc < 0:
+        raise ValueError("dt_min must be finite and > 0")
+    return (s.value, m.value, v.value) if rc == 1 else None
 
 
 def julian_to_gmst(jd):

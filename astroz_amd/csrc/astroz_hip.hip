@@ -30,6 +30,8 @@
 #include "eclipse_kernel.h"
 #include "los.h"
 #include "access_kernel.h"
+#include "conjunction.h"
+#include "conjunction_kernel.h"
 #include "tle_host.h"
 #include "host_step.h"
 
@@ -270,6 +272,10 @@ struct azh_constellation {
     DevBuf<double> d_acc_track;           // azh_find_access_host / _device: the target's own track -- positions, velocities, error bytes ...
     DevBuf<azh_access> d_acc_out;         // ... and the records / state matrix of azh_find_access_host (counts: d_pass_n)
     DevBuf<unsigned char> d_acc_state;
+    DevBuf<double> d_conj_track;          // azh_find_conjunctions_*: the targets' tracks -- positions, velocities, error bytes, one per distinct row ...
+    std::vector<unsigned> h_conj_slots;   // ... the track and the catalog row of every slot of the last call, and their grow-only
+    DevBuf<unsigned> d_conj_slots;        // device copy ...
+    DevBuf<azh_conjunction> d_conj_out;   // ... and the records of azh_find_conjunctions_host (count: d_pass_n)
     unsigned cached_n_times = 0;
     int cached_mode = 0;
     unsigned off_cat = 0; // d_list + off_cat: near-earth members in plain catalog order (k_tiles_fast: runs of consecutive rows)
@@ -3091,6 +3097,159 @@ int32_t azh_find_access_host(azh_constellation *c, const double *times, size_t n
         back(state, c->d_acc_state.p, n_state);
         if (!hip_ok(hipStreamSynchronize(c->s_main), "sync") && rc == AZ_OK) rc = AZ_ERR_HIP;
         return rc;
+    });
+}
+
+// ---- refined close approaches between a fleet of targets and the catalog ---------------------------------------------------
+int32_t azh_closest_approach(const double d0[3], const double w0[3], const double d1[3], const double w1[3], double dt_min,
+                             double *sigma, double *miss_km, double *rel_speed_km_s)
+{
+    if (!d0 || !w0 || !d1 || !w1 || !std::isfinite(dt_min) || !(dt_min > 0.0)) return -1;
+    if (!az_ca_bracket(az_ca_dot(d0, w0), az_ca_dot(d1, w1))) return 0;
+    const AzApproach a = az_ca_refine(d0, w0, d1, w1, dt_min);
+    if (sigma) *sigma = a.sigma;
+    if (miss_km) *miss_km = a.miss;
+    if (rel_speed_km_s) *rel_speed_km_s = a.speed;
+    return 1;
+}
+
+static constexpr size_t kConjMaxBlocks = size_t(1) << 22;
+// the argument rules of both variants that need neither the handle nor a device
+static int32_t conjunction_args(const double *times, size_t n_times, size_t n_targets, double threshold_km, size_t max_events)
+{
+    if (!std::isfinite(threshold_km) || !(threshold_km > 0.0) || n_targets == 0 || n_targets > 0xffffffffu || max_events > 0xffffffffu ||
+        n_times > 0xffffffffu)
+        return AZ_ERR_VALUE;
+    size_t bytes;
+    if (__builtin_mul_overflow(max_events, sizeof(azh_conjunction), &bytes) || __builtin_mul_overflow(n_targets, n_times, &bytes) ||
+        __builtin_mul_overflow(bytes, size_t(64), &bytes))
+        return AZ_ERR_VALUE;
+    // the scan: one workgroup per (chunk of 63 grid intervals, group of AZ_CONJ_GROUP slots) and row slice
+    const size_t n_groups = (n_targets + AZ_CONJ_GROUP - 1) / AZ_CONJ_GROUP;
+    const size_t n_chunks = n_times < 2 ? 0 : (n_times - 1 + AZ_CONJ_STEP - 1) / AZ_CONJ_STEP;
+    if (n_groups * n_chunks > kConjMaxBlocks) return AZ_ERR_VALUE;
+    return !times || times_increasing(times, n_times) ? AZ_OK : AZ_ERR_VALUE;
+}
+
+// azh_find_conjunctions_*: TEME states with velocities in the pass finders' scratch, k_conjunctions behind every window's
+// propagation.  The targets' tracks: when the whole catalog is one row window they are its rows of the scratch themselves (a
+// slot's track is its catalog row: nothing is launched or copied); otherwise one track per distinct row, in row order, is put
+// into d_conj_track by one-row-window launches behind the staged time axis, one per run of consecutive rows.  The slots'
+// tables travel like the stations do.
+static int32_t find_conjunctions(azh_constellation *c, const double *times, size_t n_times, const double *offsets, const size_t *targets,
+                                 size_t n_targets, double threshold_km, azh_conjunction *d_out, size_t max_events, uint32_t *d_n,
+                                 hipStream_t st)
+{
+    // (pass_windows' rule) the rows of one window; grids of fewer than 32 points run on the lane = satellite kernels, whose
+    // satellite-major store path writes whole groups of rows: they are never given a row window here
+    const size_t rows_w = std::max<size_t>(1, std::min(c->n, kPassScratch / std::max<size_t>(1, n_times * (6 * sizeof(double) + 1))));
+    const bool one_window = rows_w >= c->n;
+    if (!one_window && n_times < 32) return AZ_ERR_VALUE;
+    HIP_TRY(hipMemsetAsync(d_n, 0, sizeof(uint32_t), st));
+    if (c->n == 0 || n_times < 2) return AZ_OK;
+    std::vector<size_t> rows(targets, targets + n_targets);
+    std::sort(rows.begin(), rows.end());
+    rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
+    const size_t n_tr = one_window ? 0 : rows.size(), cells = n_tr * n_times, words = 6 * cells + (cells + 7) / 8;
+    if (c->d_conj_track.cap < words || (!c->h_conj_slots.empty() && c->d_conj_slots.cap < 2 * n_targets))
+        HIP_TRY(hipStreamSynchronize(st)); // (a scan in flight reads them)
+    if (c->d_conj_track.ensure(words) != AZ_OK || c->d_conj_slots.ensure(2 * n_targets) != AZ_OK) return AZ_ERR_HIP;
+    c->h_conj_slots.resize(2 * n_targets);
+    for (size_t k = 0; k < n_targets; ++k) {
+        c->h_conj_slots[k] = (unsigned)(one_window ? targets[k] : std::lower_bound(rows.begin(), rows.end(), targets[k]) - rows.begin());
+        c->h_conj_slots[n_targets + k] = (unsigned)targets[k];
+    }
+    HIP_TRY(hipMemcpyAsync(c->d_conj_slots.p, c->h_conj_slots.data(), sizeof(unsigned) * 2 * n_targets, hipMemcpyHostToDevice, st));
+    double *d_tpos = c->d_conj_track.p, *d_tvel = d_tpos + 3 * cells;
+    unsigned char *d_terr = reinterpret_cast<unsigned char *>(d_tpos + 6 * cells);
+    const size_t n_groups = (n_targets + AZ_CONJ_GROUP - 1) / AZ_CONJ_GROUP, n_chunks = (n_times - 1 + AZ_CONJ_STEP - 1) / AZ_CONJ_STEP;
+    // row slices: enough workgroups to fill the device when the chunks and groups alone are few
+    const size_t blocks = n_groups * n_chunks, want_blocks = 2048;
+    return pass_windows(c, times, n_times, offsets, 0.0, AZ_OUT_TEME, nullptr, 0, st, [&](size_t lo, size_t hi) -> int32_t {
+        if (lo == 0 && !one_window) { // (the time axis is on the device from here on) rows [a, b) of arrays based so that row a is track u
+            for (size_t u = 0; u < n_tr;) {
+                size_t e = u + 1;
+                while (e < n_tr && rows[e] == rows[e - 1] + 1) ++e;
+                const uintptr_t shift = (rows[u] - u) * n_times; // (rows[u] >= u: distinct, ascending)
+                const uintptr_t pb = reinterpret_cast<uintptr_t>(d_tpos) - 3 * shift * sizeof(double);
+                const uintptr_t vb = reinterpret_cast<uintptr_t>(d_tvel) - 3 * shift * sizeof(double);
+                const uintptr_t eb = reinterpret_cast<uintptr_t>(d_terr) - shift;
+                if (int32_t rc = launch_all(c, reinterpret_cast<double *>(pb), reinterpret_cast<double *>(vb), AZ_LAYOUT_SAT_MAJOR, 0,
+                                            reinterpret_cast<uint8_t *>(eb), st, 0, rows[u], rows[u] + (e - u));
+                    rc != AZ_OK)
+                    return rc;
+                u = e;
+            }
+        }
+        const size_t tiles = (hi - lo + AZ_CONJ_WAVES - 1) / AZ_CONJ_WAVES;
+        const size_t slices = std::max<size_t>(1, std::min<size_t>({tiles, (want_blocks + blocks - 1) / blocks, 65535}));
+        ConjunctionArgs q{};
+        q.pos = c->d_pass_pos.p; q.vel = c->d_pass_vel.p; q.err = c->d_pass_err.p;
+        q.times = c->d_times.p;
+        if (one_window) { q.tpos = q.pos; q.tvel = q.vel; q.terr = q.err; }
+        else { q.tpos = d_tpos; q.tvel = d_tvel; q.terr = d_terr; }
+        q.slot_track = c->d_conj_slots.p; q.slot_row = c->d_conj_slots.p + n_targets;
+        q.n_times = (unsigned)n_times; q.row0 = (unsigned)lo; q.n_rows = (unsigned)(hi - lo);
+        q.slice_rows = (unsigned)((tiles + slices - 1) / slices * AZ_CONJ_WAVES);
+        q.n_targets = (unsigned)n_targets; q.n_groups = (unsigned)n_groups;
+        q.threshold = threshold_km;
+        q.out = d_out; q.max_events = (unsigned)max_events; q.n_events = d_n;
+        const unsigned gz = (unsigned)((q.n_rows + q.slice_rows - 1) / q.slice_rows);
+        hipLaunchKernelGGL(k_conjunctions, dim3((unsigned)blocks, 1, gz), dim3(64 * AZ_CONJ_WAVES), 0, st, q);
+        HIP_TRY(hipGetLastError());
+        return AZ_OK;
+    });
+}
+
+// the rules that need the handle: every target a row of it (an empty handle reports nothing, whatever the targets)
+static int32_t conjunction_targets(const azh_constellation *c, const size_t *targets, size_t n_targets)
+{
+    for (size_t k = 0; c->n && k < n_targets; ++k)
+        if (targets[k] >= c->n) return AZ_ERR_VALUE;
+    return AZ_OK;
+}
+
+int32_t azh_find_conjunctions_device(azh_constellation *c, const double *times, size_t n_times, const double *offsets, const size_t *targets,
+                                     size_t n_targets, double threshold_km, azh_conjunction *d_out, size_t max_events, uint32_t *d_n_events,
+                                     void *stream)
+{
+    return guarded([&]() -> int32_t {
+        if (int32_t rc = conjunction_args(times, n_times, n_targets, threshold_km, max_events); rc != AZ_OK) return rc;
+        if (!c || !d_n_events || !targets || (n_times && !times) || (max_events && !d_out)) return AZ_ERR_NULL_POINTER;
+        if (int32_t rc = conjunction_targets(c, targets, n_targets); rc != AZ_OK) return rc;
+        if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
+        return find_conjunctions(c, times, n_times, offsets, targets, n_targets, threshold_km, d_out, max_events, d_n_events,
+                                 stream ? (hipStream_t)stream : c->s_main);
+    });
+}
+
+int32_t azh_find_conjunctions_host(azh_constellation *c, const double *times, size_t n_times, const double *offsets, const size_t *targets,
+                                   size_t n_targets, double threshold_km, azh_conjunction *out, size_t max_events, uint32_t *n_events)
+{
+    return guarded([&]() -> int32_t {
+        if (int32_t rc = conjunction_args(times, n_times, n_targets, threshold_km, max_events); rc != AZ_OK) return rc;
+        if (!c || !n_events || !targets || (n_times && !times) || (max_events && !out)) return AZ_ERR_NULL_POINTER;
+        if (int32_t rc = conjunction_targets(c, targets, n_targets); rc != AZ_OK) return rc;
+        if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
+        if (c->d_conj_out.cap < max_events || c->d_pass_n.cap < 1) HIP_TRY(hipStreamSynchronize(c->s_main));
+        if ((max_events && c->d_conj_out.ensure(max_events) != AZ_OK) || c->d_pass_n.ensure(1) != AZ_OK) return AZ_ERR_HIP;
+        // (the first failure wins; the final sync always runs)
+        int32_t rc = find_conjunctions(c, times, n_times, offsets, targets, n_targets, threshold_km, max_events ? c->d_conj_out.p : nullptr,
+                                       max_events, c->d_pass_n.p, c->s_main);
+        if (rc == AZ_OK && !hip_ok(hipMemcpyAsync(n_events, c->d_pass_n.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->s_main), "D2H"))
+            rc = AZ_ERR_HIP;
+        if (!hip_ok(hipStreamSynchronize(c->s_main), "sync") && rc == AZ_OK) rc = AZ_ERR_HIP;
+        if (rc != AZ_OK) return rc;
+        const size_t kept = std::min<size_t>(*n_events, max_events);
+        if (kept == 0) return AZ_OK;
+        HIP_TRY(hipMemcpyAsync(out, c->d_conj_out.p, sizeof(azh_conjunction) * kept, hipMemcpyDeviceToHost, c->s_main));
+        HIP_TRY(hipStreamSynchronize(c->s_main));
+        std::sort(out, out + kept, [](const azh_conjunction &a, const azh_conjunction &b) {
+            if (a.target != b.target) return a.target < b.target;
+            if (a.sat != b.sat) return a.sat < b.sat;
+            return a.t_tca_min < b.t_tca_min;
+        });
+        return AZ_OK;
     });
 }
 

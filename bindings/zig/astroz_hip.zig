@@ -244,6 +244,24 @@ pub extern "c" fn azh_find_access_track_device(h: ?*Handle, times_min: [*]const 
     d_track_pos: [*]const f64, d_track_vel: [*]const f64, exclude_index: usize, grazing_alt_km: f64, max_range_km: f64,
     d_out: ?[*]Access, max_windows: usize, d_n_windows: [*]u32, d_state_or_null: ?[*]u8, stream: ?*anyopaque) i32;
 
+// refined close approaches between a fleet of targets and every member
+pub extern "c" fn azh_closest_approach(d0: *const [3]f64, w0: *const [3]f64, d1: *const [3]f64, w1: *const [3]f64, dt_min: f64,
+    sigma: ?*f64, miss_km: ?*f64, rel_speed_km_s: ?*f64) i32; // 1 bracket (outputs written), 0 none
+pub const Conjunction = extern struct {
+    t_tca_min: f64,
+    miss_km: f64,
+    rel_speed_km_s: f64,
+    target: u32, // slot in targets[]
+    sat: u32, // catalog row
+    grid_index: u32, // left end of the bracket
+    reserved: u32,
+};
+pub extern "c" fn azh_find_conjunctions_host(h: ?*Handle, times_min: [*]const f64, n_times: usize, epoch_offsets_min: ?[*]const f64,
+    targets: [*]const usize, n_targets: usize, threshold_km: f64, out: ?[*]Conjunction, max_events: usize, n_events: *u32) i32;
+pub extern "c" fn azh_find_conjunctions_device(h: ?*Handle, times_min: [*]const f64, n_times: usize, epoch_offsets_min: ?[*]const f64,
+    targets: [*]const usize, n_targets: usize, threshold_km: f64, d_out: ?[*]Conjunction, max_events: usize, d_n_events: *u32,
+    stream: ?*anyopaque) i32;
+
 // one process, several devices: replaces the std.Thread fan-out of Constellation.propagateConstellation
 // (src/Constellation.zig L557-603)
 pub const Group = opaque {};

@@ -429,6 +429,51 @@ int32_t azh_find_access_track_device(azh_constellation *c, const double *times_m
                                      double grazing_alt_km, double max_range_km, azh_access *d_out, size_t max_windows,
                                      uint32_t *d_n_windows, uint8_t *d_state_or_null, void *stream);
 
+/* Closest approach inside one grid interval.  d0, w0 / d1, w1: the relative position (km) and velocity (km/s) of two objects
+ * at the ends of an interval of dt_min minutes.  The interval is a BRACKET when d0.w0 < 0 and d1.w1 >= 0 (the distance falls
+ * at the left end and no longer falls at the right end).  On a bracket the relative track is the cubic Hermite interpolant of
+ * d, component by component, with end slopes 60 dt_min w, and the closest approach is the root in [0, 1] of d(sigma).d'(sigma)
+ * (regula falsi with the Illinois correction): *sigma = its place in the interval, *miss_km = |d(sigma)|, *rel_speed_km_s =
+ * |d'(sigma)| / (60 dt_min); any of the three may be NULL.  Returns 1 for a bracket, 0 otherwise with the outputs untouched,
+ * -1 when a vector is NULL or dt_min is not finite and > 0.  Pure host function, the twin of the kernel's arithmetic. */
+int32_t azh_closest_approach(const double d0[3], const double w0[3], const double d1[3], const double w1[3], double dt_min,
+                             double *sigma, double *miss_km, double *rel_speed_km_s);
+
+/* Refined close approaches between a fleet of targets and the catalog (no reference counterpart): every approach of member s
+ * to target slot k (row targets[k] of the handle; s != targets[k]) below threshold_km over the grid times_min (tsince as
+ * azh_propagate_*), with its time, miss distance and relative speed.
+ * The handle is propagated in AZ_OUT_TEME with velocities into the pass finders' device scratch (row windows of at most
+ * ~512 MiB; the targets' tracks are its rows there, or with several windows propagated into a buffer of the handle first), and a
+ * kernel tests every (slot, row, grid interval): the
+ * interval [i, i + 1] is a bracket (azh_closest_approach, d = r_s - r_target) when both objects propagated at both ends, and
+ * an EVENT when the refined miss is below threshold_km.  Nothing is propagated again.  Not events: a minimum at the first or
+ * last grid time, a minimum next to a failed point of either object, an interval that holds a maximum and a minimum together
+ * (the sign of d.w is then the same at both ends), anything in a target's own row (a member with the target's very elements
+ * has d = 0 throughout and no bracket either).  Duplicate entries of targets are allowed: each slot reports its own events.
+ * Light time, covariance and probability of collision are not modelled.
+ * d_out: max_events records; *d_n_events = the TRUE number of events (may exceed max_events: which of them are stored, and
+ * the order of the list, are then / always unspecified in the _device form); max_events == 0 counts only.  _host: the
+ * min(*n_events, max_events) stored records come back sorted by (target, sat, t_tca_min).  n_times < 2 or an empty handle: a
+ * zero count.
+ * AZ_ERR_VALUE, checked first and without touching a device: times_min not strictly increasing, threshold_km not finite or
+ * <= 0, n_targets == 0, max_events > 0xffffffff, sizes that overflow; then, of the handle: a target >= n_sats, or a grid of
+ * fewer than 32 points on a catalog too large for one row window (more than 340,000 satellites).
+ * AZ_ERR_NULL_POINTER: a missing handle, times_min, targets, counter, or d_out with max_events > 0.
+ * _device: d_out / d_n_events (one uint32_t) on c's device, asynchronous on `stream` (NULL = the handle's). */
+typedef struct azh_conjunction {
+    double t_tca_min, miss_km, rel_speed_km_s; /* on the caller's time axis, refined (above); km; km/s */
+    uint32_t target;     /* slot in targets[] */
+    uint32_t sat;        /* catalog row */
+    uint32_t grid_index; /* left end i of the bracket */
+    uint32_t reserved;   /* 0 */
+} azh_conjunction;
+int32_t azh_find_conjunctions_host(azh_constellation *c, const double *times_min, size_t n_times, const double *epoch_offsets_min,
+                                   const size_t *targets, size_t n_targets, double threshold_km, azh_conjunction *out,
+                                   size_t max_events, uint32_t *n_events);
+int32_t azh_find_conjunctions_device(azh_constellation *c, const double *times_min, size_t n_times, const double *epoch_offsets_min,
+                                     const size_t *targets, size_t n_targets, double threshold_km, azh_conjunction *d_out,
+                                     size_t max_events, uint32_t *d_n_events, void *stream);
+
 /* Fused single-target conjunction screen = Constellation.screenConstellation
  * (src/Constellation.zig L683-756; Python: Sgp4Constellation.screen_conjunction,
  * bindings/python/astroz/__init__.py L625-632).  For every satellite the minimum distance (km) to
