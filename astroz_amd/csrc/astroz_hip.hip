@@ -217,6 +217,7 @@ struct azh_constellation {
         DevBuf<unsigned char> flag;
         DevBuf<unsigned> redo;
     } plan[4]; // ([3]: the lane = satellite time-major kernel, k_cols_fast)
+    int last_plan = -1;         // the plan the most recent launch set read (azh_last_window_tiers); -1: none
     DevBuf<double> d_inc;       // uniform grids: per-satellite rotation increments (k_prep_inc), [2 * AZ_INC_NUM][n_pad]
     DevBuf<double> d_fast_rec;  // ... and the record of folded constants of the lane = time fast kernels (k_prep_rec), [n_pad][FR_NUM]
     double uniform_step = 0.0;  // step of the staged grid if it is uniform, else 0
@@ -296,6 +297,7 @@ struct azh_constellation {
         unsigned fails;                 // failed captures of this key; from the second on the key runs eagerly for good
         hipGraph_t graph;
         hipGraphExec_t exec;
+        int plan = -1;                  // the window plan the launch set reads (last_plan)
     };
     std::vector<LaunchGraph> graphs;
     int graphs_on = 0;         // azh_set_graphs / ASTROZ_AMD_GRAPHS (off by default: measured, it only pays for multi-window pipelines)
@@ -905,6 +907,7 @@ int32_t stage_inputs(azh_constellation *c, const double *times, size_t n_times, 
     c->seeds_valid = false; // new time grid / offsets
     drop_graphs(c);          // (captured launch sets hold the old grid's buffers and shapes)
     for (auto &pl : c->plan) pl.valid = false;
+    c->last_plan = -1;
     // uniform grid?  times[i] == times[0] + i*step up to the rounding of the grid itself: the fast step
     // (fast_step.h) then advances its carried angles by per-satellite constant rotations
     c->uniform_step = 0.0;
@@ -1048,6 +1051,7 @@ int32_t ensure_plan(azh_constellation *c, PropArgs &a, const FastShape &shape, h
             pl.flag.ensure((size_t)n_list * n_seg) != AZ_OK)
             return AZ_ERR_HIP;
         HIP_TRY(hipMemsetAsync(pl.redo.p, 0, 4 * sizeof(unsigned), st));
+        HIP_TRY(hipMemsetAsync(pl.flag.p, 0, (size_t)n_list * n_seg, st)); // (entries past a slot's last segment stay without AZ_PLAN_SET)
         PlanArgs q{};
         q.el = a.el; q.flags = a.flags; q.n_pad = a.n_pad; q.list = a.list; q.n_list = n_list; q.n_circ = a.n_circ;
         q.n_times = a.n_times; q.tile_c = shape.tile_c; q.tile_e = shape.tile_e; q.by_flags = shape.kind == 2 ? 1u : 0u;
@@ -1064,6 +1068,7 @@ int32_t ensure_plan(azh_constellation *c, PropArgs &a, const FastShape &shape, h
         pl.valid = true;
         pl.tile_c = shape.tile_c; pl.tile_e = shape.tile_e; pl.n_list = n_list; pl.n_seg = n_seg; pl.parity = 0; pl.mixed32 = shape.mixed32;
     }
+    c->last_plan = (int)shape.kind;
     a.plan_win = pl.win.p;
     a.plan_flag = pl.flag.p;
     a.plan_stride = n_list;
@@ -1114,6 +1119,7 @@ int32_t launch_all(azh_constellation *c, double *d_pos, double *d_vel, int layou
     if (row_lo >= row_hi) return AZ_OK;
     if (stride == 0) stride = c->n;
     if (layout == AZ_LAYOUT_TIME_MAJOR && stride < c->n) return AZ_ERR_VALUE;
+    c->last_plan = -1; // (ensure_plan names the plan this launch set reads, if any)
 
     PropArgs a{};
     a.el = c->d_el.p;
@@ -1312,6 +1318,7 @@ int32_t launch_cached(azh_constellation *c, double *d_pos, double *d_vel, int la
         HIP_TRY(hipGraphLaunch(hit->exec, st));
         for (unsigned k = 0; k < 4; ++k) c->plan[k].parity = (hit->sig_after >> k) & 1u;
         c->last_path = hit->path;
+        c->last_plan = hit->plan;
         HIP_TRY(hipEventRecord(c->ev_graph, st));
         return AZ_OK;
     }
@@ -1354,6 +1361,7 @@ int32_t launch_cached(azh_constellation *c, double *d_pos, double *d_vel, int la
     pending->exec = exec;
     pending->sig_after = plan_sig(c);
     pending->path = c->last_path;
+    pending->plan = c->last_plan;
     HIP_TRY(hipGraphLaunch(exec, st));
     HIP_TRY(hipEventRecord(c->ev_graph, st));
     return AZ_OK;
@@ -3412,6 +3420,31 @@ int32_t azh_last_one_stats(azh_constellation *c, uint32_t *n_segments, uint32_t 
     unsigned cnt = 0;
     for (unsigned k = 0; k < AZ_ONE_LISTS; ++k) cnt += head[32u * k];
     *n_handed_over = cnt;
+    return AZ_OK;
+}
+
+int32_t azh_last_window_tiers(azh_constellation *c, uint32_t counts[AZH_WINDOW_TIER_COUNTS])
+{
+    if (!c || !counts) return AZ_ERR_NULL_POINTER;
+    for (unsigned k = 0; k < AZH_WINDOW_TIER_COUNTS; ++k) counts[k] = 0;
+    if (c->last_plan < 0 || !c->plan[c->last_plan].valid) return AZ_OK;
+    const azh_constellation::FastPlan &pl = c->plan[c->last_plan];
+    if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
+    HIP_TRY(hipDeviceSynchronize()); // (the plan is built on the stream of the call that staged it)
+    std::vector<unsigned char> f;
+    try {
+        f.resize((size_t)pl.n_list * pl.n_seg);
+    } catch (const std::bad_alloc &) {
+        return AZ_ERR_HIP;
+    }
+    if (f.empty()) return AZ_OK;
+    HIP_TRY(hipMemcpy(f.data(), pl.flag.p, f.size(), hipMemcpyDeviceToHost));
+    for (unsigned char v : f) {
+        if (!(v & AZ_PLAN_SET)) continue;
+        if (!(v & AZ_PLAN_OK)) ++counts[AZH_WINDOW_TIER_REJECTED];
+        else if (v & AZ_PLAN_ECC) ++counts[AZH_WINDOW_TIER_ECC];
+        else ++counts[((v >> AZ_PLAN_TIER_SHIFT) & AZ_PLAN_TIER_MASK) ? AZH_WINDOW_TIER_EPS : AZH_WINDOW_TIER_GENERAL];
+    }
     return AZ_OK;
 }
 

@@ -413,6 +413,19 @@ AZ_DEVICE void az_fpq_milli(double d, const RC &k, double &p, double &q)
 #define AZ_FAST_EL2 1.6e-5
 #define AZ_FAST_TEMP2 6.0e-4
 
+// Body tiers of the near-circular step.  The widest rotation tier of the general body, the 1/16-rad polynomial for eps (what
+// is left of the along-track phase), is only needed by a third of the windows: a tier is a property of the (satellite,
+// window), decided HERE from the same bounds that validate the window, stored with the plan's flag, and selected by the row
+// kernel once per wave in front of its loop.
+//   AZ_TIER_GENERAL   |eps| <= 1/8: the 1/16-rad polynomial (as before)
+//   AZ_TIER_EPS       |eps| <= 2^-10: U turns by az_rotate_tiny2 (dropped eps^4/24 < 3.8e-14 rad = 3e-10 km at 8,000 km)
+// The general body is valid in every accepted window, the eps body only where its bound holds.  (A third body, which also
+// took the node's rotation a_nd <= 2^-7 by the 2^-7 polynomial, two instructions less, measured SLOWER than these two on the
+// device and is not kept: DESIGN 4a.)
+enum { AZ_TIER_GENERAL = 0, AZ_TIER_EPS = 1, AZ_TIER_NUM = 2 };
+#define AZ_TIER_EPS_MAX 0.0009765625 /* 2^-10 */
+#define AZ_FAST_EM_MIN 1.0e-6        /* the generic step clamps em here; the fast step does not, so its windows stay above it */
+
 // Validation, once per time window instead of once per step.  The step below is straight-line code for the case
 // "every small angle sits inside its polynomial tier, the orbit is near-circular (ECC = false)".  Each of those
 // conditions is bounded here rigorously over the whole window [t_a, t_b] of tsince values from the satellite's
@@ -422,8 +435,9 @@ AZ_DEVICE void az_fpq_milli(double d, const RC &k, double &p, double &q)
 // per cent wider than the quantities themselves, which moves well under 1 % more segments there.
 // ECC = true additionally validates its Newton iteration per step (az_sgp4_fast_step's return value).
 // dmax: largest |delta_i| of a quasi-uniform grid (0: exactly uniform): every time bound widens by it, eps by |udot| dmax.
+// Returns the window's body tier (AZ_TIER_*; ECC: AZ_TIER_GENERAL), or -1 where a bound fails.
 template <bool ECC>
-AZ_DEVICE bool az_fast_window_ok(const FastK &k, const AzGrav &g, double t_a, double t_b, double dmax = 0.0)
+AZ_DEVICE int az_fast_window_tier(const FastK &k, const AzGrav &g, double t_a, double t_b, double dmax = 0.0)
 {
     const double T = fmax(fabs(t_a), fabs(t_b)) + dmax;
     const double ae = fabs(k.eta_);
@@ -431,8 +445,10 @@ AZ_DEVICE bool az_fast_window_ok(const FastK &k, const AzGrav &g, double t_a, do
     const double th = fma(fabs(k.xmcof_), ae * fma(2.0 * ae, ae, 6.0), fabs(k.omgcof_) * T);
     // tempa = 1 - t (cc1 + t (d2 + t (d3 + t d4)))
     const double da = T * fma(T, fma(T, fma(T, fabs(k.d4_), fabs(k.d3_)), fabs(k.d2_)), fabs(k.cc1_));
-    const double em = fabs(k.ecb_) + fma(fabs(k.bc4_), T, fabs(k.bc5_));
+    const double dem = fma(fabs(k.bc4_), T, fabs(k.bc5_)); // em = ecb - bc4 t - bc5 sin(M + th)
+    const double em = fabs(k.ecb_) + dem;
     bool ok = (th <= AZ_ROT_16TH) & (da <= 0.25) & (em <= 0.9);
+    ok &= k.ecb_ - dem >= AZ_FAST_EM_MIN;                     // em >= ecb - |bc4| T - |bc5|: the step carries no clamp
     const double sam = k.sab_ * (1.0 - da);                  // sqrt(am) >= sam
     const double inv_am = 1.0 / (sam * sam);                 // 1/am <= inv_am
     const double temp = inv_am / fma(-em, em, 1.0);          // temp = 1/(am (1 - em^2))
@@ -451,15 +467,28 @@ AZ_DEVICE bool az_fast_window_ok(const FastK &k, const AzGrav &g, double t_a, do
     // a_nd = k_node temp2 sin2u + nodedot (t - tmid) + xnodcf t^2
     const double a_nd = fma(fabs(k.k_node_), temp2, fma(fabs(k.nodedot_), 0.5 * fabs(t_b - t_a) + dmax, fabs(k.xnodcf_) * T * T));
     ok &= a_nd <= AZ_ROT_MED;
-    return ok; // (every comparison is false for a NaN operand)
+    if (!ok) return -1; // (every comparison is false for a NaN operand)
+    return (!ECC && eps <= AZ_TIER_EPS_MAX) ? AZ_TIER_EPS : AZ_TIER_GENERAL;
 }
+template <bool ECC>
+AZ_DEVICE bool az_fast_window_ok(const FastK &k, const AzGrav &g, double t_a, double t_b, double dmax = 0.0)
+{
+    return az_fast_window_tier<ECC>(k, g, t_a, t_b, dmax) >= 0;
+}
+
+// Host emulation only: a test may define AZ_FAST_PROBE(name, value) to watch the quantities the window bounds are about
+// (th, em, eps, a_nd) at every grid point.  Expands to nothing everywhere else.
+#ifndef AZ_FAST_PROBE
+#define AZ_FAST_PROBE(name, value)
+#endif
 
 // one near-earth propagation on a uniform grid, inside a window az_fast_window_ok accepted.  Returns true when
 // the eccentric form's Newton iteration left its assumptions for this lane (ECC = true only; the caller must then
 // discard r/v and use az_sgp4_step); the near-circular form always returns false.
 // DELTA (0 none, 1 tight, 2 wide): the grid is quasi-uniform; t is the ACTUAL time of this point and dl = t - (its place on the
 // ideal grid the carried pairs advance along), |dl| <= AZ_DELTA_MAX (tight) / AZ_DELTA_WIDE_MAX (wide).
-template <bool VEL, bool ECC = false, int DELTA = 0, class K = FastK, class RC = RotCoefLit>
+// TIER: the body tier az_fast_window_tier assigned to the window (near-circular form; AZ_TIER_GENERAL is valid in all).
+template <bool VEL, bool ECC = false, int DELTA = 0, int TIER = AZ_TIER_GENERAL, class K = FastK, class RC = RotCoefLit>
 AZ_DEVICE bool az_sgp4_fast_step(const K &k, const AzGrav &g, const RC &rk, double t, FastCarry &st, double r[3],
                                   double v[3], double dl = 0.0)
 {
@@ -507,7 +536,9 @@ AZ_DEVICE bool az_sgp4_fast_step(const K &k, const AzGrav &g, const RC &rk, doub
     const double smm = fma(cA, p, fma(sA, q, sA));            // sin(M + th)
     const double sw = fma(-cW, p, fma(sW, q, sW));            // (sin,cos)(W - th)
     const double cw = fma(sW, p, fma(cW, q, cW));
-    const double em = fmax(fma(-k.bc5(), smm, fma(-k.bc4(), t, k.ecb())), 1.0e-6);
+    const double em = fma(-k.bc5(), smm, fma(-k.bc4(), t, k.ecb())); // (>= AZ_FAST_EM_MIN over the window: no clamp)
+    AZ_FAST_PROBE(th, th)
+    AZ_FAST_PROBE(em, em)
 
     // am = a_base tempa^2: one reciprocal gives 1/sqrt(am) and 1/(am (1 - em^2))
     const double sqrt_am = k.sab() * fabs(tempa);
@@ -523,8 +554,12 @@ AZ_DEVICE bool az_sgp4_fast_step(const K &k, const AzGrav &g, const RC &rk, doub
     double s = st.sU, c = st.cU;
     {
         const double eps = fma(temp * k.xlcof(), axnl, nl);
-        az_pq_16th(eps, rk, p, q);
-        az_rot_apply2(s, c, p, q);
+        AZ_FAST_PROBE(eps, eps)
+        if constexpr (!ECC && TIER >= AZ_TIER_EPS) az_rotate_tiny2(s, c, eps, rk); // |eps| <= 2^-10 over the window
+        else {
+            az_pq_16th(eps, rk, p, q);
+            az_rot_apply2(s, c, p, q);
+        }
     }
 
     const double el2 = fma(axnl, axnl, aynl * aynl);
@@ -608,32 +643,31 @@ AZ_DEVICE bool az_sgp4_fast_step(const K &k, const AzGrav &g, const RC &rk, doub
     // J2 short-period corrections as tiny rotations (each bounded by 1.5 temp2 <= 9e-4); the node's own motion
     // about the window centre, nodedot (t - tmid) + xnodcf t^2, rides on the node correction
     const double a_nd = fma(k.k_node(), t2s, fma(k.nodedot(), t - k.tmid(), k.xnodcf() * t2));
+    AZ_FAST_PROBE(a_nd, a_nd)
     double ssu = sinu, csu = cosu, sn = k.sOc(), cn = k.cOc(), si = k.sinio(), ci = k.cosio();
     az_rotate_tiny2(ssu, csu, k.k_su() * t2s, rk);
     az_pq_16th(a_nd, rk, p, q); // J2 correction + the node's motion across the window (up to ~0.03 rad over +-400 min; <= 1/8)
     az_rot_apply2(sn, cn, p, q);
     az_rotate_tiny2(si, ci, k.k_inc() * temp2 * cos2u, rk);
 
+    // r = rs u, v = mvt u + rvdot w with u = M ssu + N csu, w = M csu - N ssu, M = (-sn ci, cn ci, si), N = (cn, sn, 0):
+    // the scalars go onto (ssu, csu) first, so that M and N are applied once per vector (19 instructions for 22)
     const double xmx = -sn * ci, xmy = cn * ci;
-    const double ux = fma(xmx, ssu, cn * csu);
-    const double uy = fma(xmy, ssu, sn * csu);
-    const double uz = si * ssu;
     const double rs = mrt * g.radius_km;
-    r[0] = rs * ux;
-    r[1] = rs * uy;
-    r[2] = rs * uz;
+    const double ra_s = rs * ssu, ra_c = rs * csu;
+    r[0] = fma(xmx, ra_s, cn * ra_c);
+    r[1] = fma(xmy, ra_s, sn * ra_c);
+    r[2] = si * ra_s;
     if (VEL) {
         const double rv = ra * g.vkmpersec;         // vkmpersec / sqrt(am)
         const double vk = rv * inv_ome;             // common factor of rdotl, rvdotl (km/s)
         const double nxt = rv * inv_am * temp1;     // (nm/xke) temp1, km/s
         const double mvt = fma(-nxt * k.x1mth2(), sin2u, vk * esine);
         const double rvdot = fma(nxt, fma(k.x1mth2(), cos2u, k.k_rv()), vk * betal);
-        const double vx = fma(xmx, csu, -(cn * ssu));
-        const double vy = fma(xmy, csu, -(sn * ssu));
-        const double vz = si * csu;
-        v[0] = fma(mvt, ux, rvdot * vx);
-        v[1] = fma(mvt, uy, rvdot * vy);
-        v[2] = fma(mvt, uz, rvdot * vz);
+        const double va_s = fma(mvt, ssu, rvdot * csu), va_c = fma(mvt, csu, -(rvdot * ssu));
+        v[0] = fma(xmx, va_s, cn * va_c);
+        v[1] = fma(xmy, va_s, sn * va_c);
+        v[2] = si * va_s;
     }
     return bad;
 }

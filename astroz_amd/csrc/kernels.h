@@ -124,7 +124,7 @@ struct PropArgs {
     const double *tmp_pos, *tmp_vel;
     unsigned n_rows;
     const double *plan_win;         // [n_seg][plan_stride][AZ_PLAN_NUM]
-    const unsigned char *plan_flag; // [n_seg][plan_stride]: AZ_PLAN_OK | AZ_PLAN_TC
+    const unsigned char *plan_flag; // [n_seg][plan_stride]: AZ_PLAN_OK | AZ_PLAN_TC | tier << AZ_PLAN_TIER_SHIFT | AZ_PLAN_ECC | AZ_PLAN_SET
     unsigned plan_stride;
     const unsigned *redo_static;
     AzGrav g;
@@ -133,6 +133,10 @@ enum { AZ_ROW_NEAR = 0, AZ_ROW_COPY = 1, AZ_ROW_ZERO = 2 }; // rowmap kinds: slo
 enum { AZ_PLAN_sOc, AZ_PLAN_cOc, AZ_PLAN_sdU, AZ_PLAN_cdU, AZ_PLAN_s1U, AZ_PLAN_c1U, AZ_PLAN_NUM };
 #define AZ_PLAN_OK 1u /* the fast step's validation bounds hold over this window (az_fast_window_ok) */
 #define AZ_PLAN_TC 2u /* the drag phase is expanded about the window centre (tc = tmid), else tc = 0 */
+#define AZ_PLAN_TIER_SHIFT 2 /* bit 2: the window's body tier (fast_step.h AZ_TIER_*; 0 for the eccentric form) */
+#define AZ_PLAN_TIER_MASK 1u
+#define AZ_PLAN_ECC 16u /* the slot runs the eccentric form */
+#define AZ_PLAN_SET 32u /* the entry belongs to a (slot, segment) of the staged grid (the buffer is cleared before the plan is built) */
 
 // one result vector -> memory, fp64 or fp32
 template <class T>
@@ -710,14 +714,16 @@ __global__ void __launch_bounds__(256) k_plan_windows(PlanArgs a)
     az_load_fast(a.el, a.n_pad, s, fl, a.inc, 1, k1);
     az_fast_window(a.el, a.n_pad, s, w_a, w_b, a.step, k1);
     // a class the form cannot take (an eccentric member in the near-circular list) is rejected like a failed bound
-    bool ok = ecc ? az_fast_window_ok<true>(k0, a.g, w_a, w_b, a.delta_max) : az_fast_window_ok<false>(k0, a.g, w_a, w_b, a.delta_max);
+    const int tier = ecc ? az_fast_window_tier<true>(k0, a.g, w_a, w_b, a.delta_max) : az_fast_window_tier<false>(k0, a.g, w_a, w_b, a.delta_max);
+    bool ok = tier >= 0;
     if (!ecc && AZ_FLAG_ECLASS(fl) != 0) ok = false;
     if (!ecc && a.f32_mixed && !az_fast32p_window_ok(k0, w_a, w_b)) ok = false;
     const size_t at = (size_t)seg * a.n_list + slot;
     double *w = a.win + at * AZ_PLAN_NUM;
     w[AZ_PLAN_sOc] = k0.sOc_; w[AZ_PLAN_cOc] = k0.cOc_; w[AZ_PLAN_sdU] = k0.sdU_; w[AZ_PLAN_cdU] = k0.cdU_;
     w[AZ_PLAN_s1U] = k1.sdU_; w[AZ_PLAN_c1U] = k1.cdU_;
-    a.flag[at] = (unsigned char)((ok ? AZ_PLAN_OK : 0u) | (k0.tc_ != 0.0 ? AZ_PLAN_TC : 0u));
+    a.flag[at] = (unsigned char)((ok ? AZ_PLAN_OK | ((unsigned)tier << AZ_PLAN_TIER_SHIFT) : 0u) | (k0.tc_ != 0.0 ? AZ_PLAN_TC : 0u) |
+                                 (ecc ? AZ_PLAN_ECC : 0u) | AZ_PLAN_SET);
     if (!ok) {
         const unsigned k = atomicAdd(a.redo_static, 1u);
         a.redo_items[3 * (size_t)k + 0] = slot;
@@ -732,7 +738,7 @@ __global__ void k_plan_arm(unsigned *redo_static, unsigned *c0, unsigned *c1)
 }
 // window constants of one wave's segment from the plan (wave-uniform scalar loads)
 template <class K>
-__device__ __forceinline__ bool az_plan_window(const PropArgs &p, unsigned seg, unsigned slot, double w_a, double w_b, K &k0)
+__device__ __forceinline__ bool az_plan_window(const PropArgs &p, unsigned seg, unsigned slot, double w_a, double w_b, K &k0, unsigned *tier = nullptr)
 {
     const size_t at = (size_t)seg * p.plan_stride + slot;
     const double *w = p.plan_win + at * AZ_PLAN_NUM;
@@ -740,6 +746,7 @@ __device__ __forceinline__ bool az_plan_window(const PropArgs &p, unsigned seg, 
     k0.tmid_ = 0.5 * (w_a + w_b);
     k0.tc_ = (f & AZ_PLAN_TC) ? k0.tmid_ : 0.0;
     k0.sOc_ = w[AZ_PLAN_sOc]; k0.cOc_ = w[AZ_PLAN_cOc]; k0.sdU_ = w[AZ_PLAN_sdU]; k0.cdU_ = w[AZ_PLAN_cdU];
+    if (tier) *tier = (f >> AZ_PLAN_TIER_SHIFT) & AZ_PLAN_TIER_MASK;
     return (f & AZ_PLAN_OK) != 0;
 }
 
@@ -822,6 +829,9 @@ __device__ __forceinline__ void az_fill_fast_table(double *table, const double *
 __device__ __forceinline__ ColdBroadcast ColdBroadcast::fresh() const { return ColdBroadcast{p, az_opaque_lds(m)}; }
 #ifndef AZ_ROWSF_WAVES
 #define AZ_ROWSF_WAVES 6 /* k_rows_fast, near-circular Kepler form: 74 VGPRs; forced to 7 (70 VGPRs) or 8 (64 + spills) it measures slower */
+#endif
+#ifndef AZ_ROWS_TIERS
+#define AZ_ROWS_TIERS 1 /* k_rows_fast: one loop body per window tier (0: the general body for every window) */
 #endif
 #ifndef AZ_ROWSF32_WAVES
 #define AZ_ROWSF32_WAVES 4 /* k_rows_fast32: two grid points per lane */
@@ -1077,6 +1087,7 @@ __global__ void __launch_bounds__(64, FRAME >= 2 ? 4 : (ECC ? AZ_ROWSF_ECC_WAVES
     const unsigned t_hi = min(t_lo + p.tile, p.n_times);
     unsigned base = t_lo;
     bool window_ok;
+    unsigned tier = AZ_TIER_GENERAL; // body tier of this wave's window, from the plan (wave-uniform)
     double best_d2 = __builtin_inf(); // SINK_SCREEN: this lane's running minimum of |r - r_target|^2 and its grid point
     unsigned best_t = 0xffffffffu;
     {
@@ -1095,7 +1106,7 @@ __global__ void __launch_bounds__(64, FRAME >= 2 ? 4 : (ECC ? AZ_ROWSF_ECC_WAVES
             const double w_a = fma((double)t_lo, p.uniform_step, p.grid_t0 + off), w_b = fma((double)(t_hi - 1), p.uniform_step, p.grid_t0 + off);
             // window constants and the verdict of the validation bounds: prepared once per staged grid (k_plan_windows); a
             // rejected window is already on the redo list
-            window_ok = az_plan_window(p, blockIdx.y, row + p.redo_slot0, w_a, w_b, k);
+            window_ok = az_plan_window(p, blockIdx.y, row + p.redo_slot0, w_a, w_b, k, &tier);
             if (!window_ok) return;
             az_fast_rec_hot(rec, k); // scalar loads: the hot constants arrive in SGPRs
             az_wave_lds_fence();
@@ -1127,8 +1138,15 @@ __global__ void __launch_bounds__(64, FRAME >= 2 ? 4 : (ECC ? AZ_ROWSF_ECC_WAVES
         }
         AzRowSink sink{};
         if constexpr (SINK != AZ_SINK_SCREEN) sink = az_row_sink(prow, vrow, p.n_times);
+        // The loop, compiled once per body tier (fast_step.h AZ_TIER_*).  The tier decides, HERE and once per wave, where each
+        // loop ends: the loops follow one another on the same carried state, the wave's own runs to t_hi and the other makes no
+        // trip (one scalar compare per wave).  No iteration tests, votes on or selects by the tier.  (Written as alternatives
+        // the loops keep the seeds alive across one another -- the structurised control flow cannot see that only one of them
+        // runs: 12 VGPRs, a spill at the register limit of six waves.)
+        auto run = [&](auto tier_c, const unsigned t_end) __attribute__((always_inline)) {
+        constexpr int TIER = decltype(tier_c)::value;
 #pragma unroll 1
-        for (; window_ok && base < t_hi; base += 64) {
+        for (; window_ok && base < t_end; base += 64) {
             const unsigned i = base + lane;
             const bool live = i < t_hi;
             double t = fma((double)i, step, t_first), dl = 0.0;
@@ -1147,7 +1165,7 @@ __global__ void __launch_bounds__(64, FRAME >= 2 ? 4 : (ECC ? AZ_ROWSF_ECC_WAVES
 #if defined(AZ_ABLATE) && AZ_ABLATE == 2 /* tuning experiment: stores only */
             r[0] = t; r[1] = t + 1.0; r[2] = t + 2.0; v[0] = t + 3.0; v[1] = t + 4.0; v[2] = t + 5.0;
 #else
-            const bool bad = az_sgp4_fast_step<VEL, ECC, DELTA>(k, p.g, rk, t, fc, r, v, dl);
+            const bool bad = az_sgp4_fast_step<VEL, ECC, DELTA, TIER>(k, p.g, rk, t, fc, r, v, dl);
             if (az_any(bad && live)) break;
 #endif
             if (SINK == AZ_SINK_SCREEN) {
@@ -1189,6 +1207,10 @@ __global__ void __launch_bounds__(64, FRAME >= 2 ? 4 : (ECC ? AZ_ROWSF_ECC_WAVES
 #endif
             az_rows_store<VEL>(staged, base + 64 <= t_hi, live, lane, rows_stage, prow, vrow, base, r, v, sink);
         }
+        };
+        // (the tiered bodies: TEME rows of the near-circular form)
+        if constexpr (AZ_ROWS_TIERS && !ECC && FRAME == 0) run(std::integral_constant<int, AZ_TIER_EPS>(), tier == AZ_TIER_EPS ? t_hi : t_lo);
+        run(std::integral_constant<int, AZ_TIER_GENERAL>(), t_hi);
     }
     if (SINK == AZ_SINK_SCREEN) {
         // partial minimum of [t_lo, base) for (this form's segment, list slot); what a Newton hand-over leaves goes into the

@@ -673,6 +673,18 @@ uint32_t azh_last_path(const azh_constellation *c);
  * deep-space or failed -- one generic step per point throughout) and how many of them it handed over to the generic kernel
  * (irregular times, a window outside the fast step's bounds).  Waits for that call to finish.  Returns an astroz error code. */
 int32_t azh_last_one_stats(azh_constellation *c, uint32_t *n_segments, uint32_t *n_handed_over);
+/* the window plan behind the most recent uniform-grid launch of this handle: how many (satellite, time segment) windows carry
+ * each loop body of the branch-free step.  counts[AZH_WINDOW_TIER_GENERAL], counts[AZH_WINDOW_TIER_EPS]: near-circular form,
+ * general body / eps-small body (the satellite-major TEME row kernel runs the body of the window's tier; the other fast kernels
+ * run the general body in both); counts[AZH_WINDOW_TIER_ECC]: eccentric form; counts[AZH_WINDOW_TIER_REJECTED]: windows the
+ * validation bounds hand to the generic step.  All zero when the last staged grid has no plan (irregular grid, fast path off).  Read back from the plan when asked:
+ * waits for the device, costs nothing in a step.  Returns an astroz error code. */
+#define AZH_WINDOW_TIER_GENERAL 0
+#define AZH_WINDOW_TIER_EPS 1
+#define AZH_WINDOW_TIER_ECC 2
+#define AZH_WINDOW_TIER_REJECTED 3
+#define AZH_WINDOW_TIER_COUNTS 4
+int32_t azh_last_window_tiers(azh_constellation *c, uint32_t counts[AZH_WINDOW_TIER_COUNTS]);
 
 #ifdef __cplusplus
 }
