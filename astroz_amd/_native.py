@@ -55,7 +55,7 @@ EXPORTS = [
     "azh_num_satellites", "azh_num_sgp4", "azh_num_sdp4", "azh_get_epochs", "azh_get_status",
     "azh_get_field", "azh_propagate_host", "azh_propagate_device", "azh_propagate_device_cached", "azh_propagate_device_window",
     "azh_propagate_jd_host", "azh_synchronize", "azh_propagate_one_host", "azh_set_time_tile", "azh_set_timing", "azh_set_fast_path", "azh_set_tile_kernel", "azh_set_graphs", "azh_set_f32_arithmetic", "azh_set_f32_mode",
-    "azh_last_kernel_ms", "azh_last_path", "azh_last_one_stats", "azh_last_window_tiers", "azh_set_host_copy_threads", "azh_set_host_points", "azh_get_host_points", "azh_selftest_coords", "azh_selftest_host_step", "azh_host_alloc", "azh_host_free", "azh_host_pool_stats", "azh_host_pool_trim", "azh_propagate_device_f32", "azh_propagate_device_cached_f32",
+    "azh_last_kernel_ms", "azh_last_path", "azh_last_one_stats", "azh_last_window_tiers", "azh_last_window_ecc_tiers", "azh_set_host_copy_threads", "azh_set_host_points", "azh_get_host_points", "azh_selftest_coords", "azh_selftest_host_step", "azh_host_alloc", "azh_host_free", "azh_host_pool_stats", "azh_host_pool_trim", "azh_propagate_device_f32", "azh_propagate_device_cached_f32",
     "azh_screen_target_host", "azh_screen_target_device", "azh_coarse_screen_device", "azh_coarse_screen_host",
     "azh_screen_all_host", "azh_constellation_from_omm_json", "azh_propagate_one_device", "azh_selftest_math",
     "azh_parse_tle_text", "azh_parse_omm_json", "azh_set_parse_threads", "coords_julian_to_gmst",
@@ -275,6 +275,8 @@ def lib():
     L.azh_last_one_stats.restype = C.c_int32
     L.azh_last_window_tiers.argtypes = [vp, vp]
     L.azh_last_window_tiers.restype = C.c_int32
+    L.azh_last_window_ecc_tiers.argtypes = [vp, vp]
+    L.azh_last_window_ecc_tiers.restype = C.c_int32
     L.azh_propagate_device_f32.argtypes = L.azh_propagate_device.argtypes
     L.azh_propagate_device_f32.restype = i32
     L.azh_propagate_device_cached_f32.argtypes = L.azh_propagate_device_cached.argtypes
@@ -798,6 +800,14 @@ class DeviceConstellation:
         cnt = (C.c_uint32 * 4)()
         check(lib().azh_last_window_tiers(self._h, cnt), "azh_last_window_tiers")
         return dict(zip(("general", "eps", "ecc", "rejected"), (int(x) for x in cnt)))
+
+    def last_window_ecc_tiers(self):
+        """The accepted eccentric windows of that plan ("ecc" of last_window_tiers) per loop body of the row kernel, as a
+        dict: "e1" (near-circular Kepler form, el <= 0.01), "e2" (three Newton trips, el <= 0.1), "general" (five trips).
+        All zero without a plan.  Waits for the device."""
+        cnt = (C.c_uint32 * 3)()
+        check(lib().azh_last_window_ecc_tiers(self._h, cnt), "azh_last_window_ecc_tiers")
+        return dict(zip(("e1", "e2", "general"), (int(x) for x in cnt)))
 
 
 class DeviceGroup:

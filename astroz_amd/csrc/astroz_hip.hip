@@ -3448,6 +3448,30 @@ int32_t azh_last_window_tiers(azh_constellation *c, uint32_t counts[AZH_WINDOW_T
     return AZ_OK;
 }
 
+int32_t azh_last_window_ecc_tiers(azh_constellation *c, uint32_t counts[AZH_WINDOW_ECC_COUNTS])
+{
+    if (!c || !counts) return AZ_ERR_NULL_POINTER;
+    for (unsigned k = 0; k < AZH_WINDOW_ECC_COUNTS; ++k) counts[k] = 0;
+    if (c->last_plan < 0 || !c->plan[c->last_plan].valid) return AZ_OK;
+    const azh_constellation::FastPlan &pl = c->plan[c->last_plan];
+    if (set_device(c) != AZ_OK) return AZ_ERR_HIP;
+    HIP_TRY(hipDeviceSynchronize()); // (the plan is built on the stream of the call that staged it)
+    std::vector<unsigned char> f;
+    try {
+        f.resize((size_t)pl.n_list * pl.n_seg);
+    } catch (const std::bad_alloc &) {
+        return AZ_ERR_HIP;
+    }
+    if (f.empty()) return AZ_OK;
+    HIP_TRY(hipMemcpy(f.data(), pl.flag.p, f.size(), hipMemcpyDeviceToHost));
+    for (unsigned char v : f) {
+        if ((v & (AZ_PLAN_SET | AZ_PLAN_OK | AZ_PLAN_ECC)) != (AZ_PLAN_SET | AZ_PLAN_OK | AZ_PLAN_ECC)) continue;
+        const unsigned t = (v >> AZ_PLAN_TIER_SHIFT) & AZ_PLAN_ETIER_MASK;
+        ++counts[t == AZ_ETIER_E1 ? AZH_WINDOW_ECC_E1 : (t == AZ_ETIER_E2 ? AZH_WINDOW_ECC_E2 : AZH_WINDOW_ECC_GENERAL)];
+    }
+    return AZ_OK;
+}
+
 double azh_last_kernel_ms(azh_constellation *c)
 {
     if (!c || !c->timed) return -1.0;

@@ -426,6 +426,41 @@ enum { AZ_TIER_GENERAL = 0, AZ_TIER_EPS = 1, AZ_TIER_NUM = 2 };
 #define AZ_TIER_EPS_MAX 0.0009765625 /* 2^-10 */
 #define AZ_FAST_EM_MIN 1.0e-6        /* the generic step clamps em here; the fast step does not, so its windows stay above it */
 
+// Body tiers of the ECCENTRIC step, decided from the window's upper bound on el = |(axnl, aynl)| <= em + temp |aycof| (the
+// plan's flag carries two tier bits for an eccentric slot).  The general body pays the worst case for every member: five
+// Newton trips with the widest rotation of each trip, a per-step predicate on every correction.  Most eccentric members are
+// nowhere near it.  With Kepler's equation g(E) = u + el sin(E - w) - E = 0 started at E0 = u:  |E* - E0| <= el,  the first
+// correction |d0| <= el/(1 - el),  and a Newton trip squares the error:  |e(k+1)| <= el e(k)^2 / (2 (1 - el)).
+//   AZ_ETIER_E1   el <= AZ_ETIER_E1_MAX = 0.01: the NEAR-CIRCULAR Kepler form (one Newton trip, chord steps with the same
+//                 reciprocal, series for betal and its kin) with what each series needs at el^2 <= 1e-4 instead of 1.6e-5:
+//                   th's rotation, scaled by em <= 0.01: cos to d^6 (dropped d^8/8! 0.01 < 6e-17; the d^6/720 = 8.3e-11 term
+//                     az_pq_ecc_scaled drops would be 8.3e-13 rad here), sin to d^5 as before (d^7/5040 0.01 < 7.4e-15);
+//                   first correction |d0| <= 0.0102: sin to d^5 (dropped d^7/5040 < 3e-18; the d^5/120 az_fpq_milli drops
+//                     would be 9e-13), cos to d^4 as before (d^6/720 < 1.6e-15);
+//                   error after the Newton trip e1 <= el^3/(2 (1 - el)) = 5.1e-7; a chord step (the reciprocal of trip 0:
+//                     1 - el cos(E - w) moved by <= el |E1 - E0| <= el^2/(1 - el)) leaves e(k+1) <= e(k) el^2/(1 - el)^2:
+//                     5.2e-11 after one (the near-circular form's el = 0.004 gives 5e-13 there), 5.3e-15 after TWO;
+//                   the chord corrections |d1| <= 5.2e-7, |d2| <= 5.3e-11 turn (sin E, cos E) to first order: the dropped
+//                     d1^2/2 < 1.4e-13 is a change of the pair's LENGTH (1e-9 km of the radius), the angle is off by d1^3/3;
+//                   1/(1 - ecose) from trip 0's reciprocal, x = 1 - ome rden <= el^2/(1 - el) = 1.01e-4: to x^3 (dropped
+//                     x^4 < 1.1e-16; x^3 itself would be 1e-12);
+//                   betal = sqrt(1 - el^2) to el^4 as before (dropped el^6/16 < 6.3e-14);
+//                   1/(1 - el^2) to el^4 (dropped el^6 = 1e-12 relative on the J2 terms, < 1e-3 of the radius; el^4 itself
+//                     would be 1e-8 x 5e-4 = 5e-12);
+//                   1/(1 + betal) = 1/2 + el^2/8 as before: it only enters as esine/(1 + betal) times axnl or aynl, so the
+//                     dropped el^4/16 = 6.3e-10 is scaled by el^2: 6.3e-14.
+//                 No predicate: every bound above follows from the window's bound on el.
+//   AZ_ETIER_E2   el <= AZ_ETIER_E2_MAX = 0.1: THREE Newton trips.  |d0| <= 0.1/0.9 = 0.112 <= 1/8: az_pq_med (dropped d^11/11!
+//                 < 9e-19); e1 <= el^3/(2 (1 - el)) = 5.6e-4, so |d1| <= e1 + e2 < 6.9e-4: az_fpq_milli (d^5/120 < 1.4e-18);
+//                 e2 <= el e1^2/(2 (1 - el)) = 1.8e-8, |d2| < 2.6e-8: first order (d2^2/2 < 3.4e-16); e3 <= el e2^2/1.8 < 2e-17.
+//                 az_rcp1 is good to 2^-46 = 1.4e-14 relative: a trip's correction is off by that fraction of ITSELF (1.6e-15,
+//                 1e-17, 4e-22), which the next trip sees in its residual -- only the last one's stays.  The generic loop's
+//                 exit criterion el^2 d^4 < 4e-26 holds for d2 by the bound: 0.01 (2.6e-8)^4 = 4.6e-33.  No predicate either.
+//   AZ_TIER_GENERAL  the five-trip body with its per-step predicate and hand-over, for every other accepted window.
+enum { AZ_ETIER_E1 = 1, AZ_ETIER_E2 = 2, AZ_ETIER_NUM = 3 };
+#define AZ_ETIER_E1_MAX 0.01
+#define AZ_ETIER_E2_MAX 0.1
+
 // Validation, once per time window instead of once per step.  The step below is straight-line code for the case
 // "every small angle sits inside its polynomial tier, the orbit is near-circular (ECC = false)".  Each of those
 // conditions is bounded here rigorously over the whole window [t_a, t_b] of tsince values from the satellite's
@@ -435,7 +470,7 @@ enum { AZ_TIER_GENERAL = 0, AZ_TIER_EPS = 1, AZ_TIER_NUM = 2 };
 // per cent wider than the quantities themselves, which moves well under 1 % more segments there.
 // ECC = true additionally validates its Newton iteration per step (az_sgp4_fast_step's return value).
 // dmax: largest |delta_i| of a quasi-uniform grid (0: exactly uniform): every time bound widens by it, eps by |udot| dmax.
-// Returns the window's body tier (AZ_TIER_*; ECC: AZ_TIER_GENERAL), or -1 where a bound fails.
+// Returns the window's body tier (AZ_TIER_*; ECC: AZ_TIER_GENERAL or AZ_ETIER_*), or -1 where a bound fails.
 template <bool ECC>
 AZ_DEVICE int az_fast_window_tier(const FastK &k, const AzGrav &g, double t_a, double t_b, double dmax = 0.0)
 {
@@ -468,7 +503,8 @@ AZ_DEVICE int az_fast_window_tier(const FastK &k, const AzGrav &g, double t_a, d
     const double a_nd = fma(fabs(k.k_node_), temp2, fma(fabs(k.nodedot_), 0.5 * fabs(t_b - t_a) + dmax, fabs(k.xnodcf_) * T * T));
     ok &= a_nd <= AZ_ROT_MED;
     if (!ok) return -1; // (every comparison is false for a NaN operand)
-    return (!ECC && eps <= AZ_TIER_EPS_MAX) ? AZ_TIER_EPS : AZ_TIER_GENERAL;
+    if (ECC) return el <= AZ_ETIER_E1_MAX ? (int)AZ_ETIER_E1 : (el <= AZ_ETIER_E2_MAX ? (int)AZ_ETIER_E2 : (int)AZ_TIER_GENERAL);
+    return eps <= AZ_TIER_EPS_MAX ? AZ_TIER_EPS : AZ_TIER_GENERAL;
 }
 template <bool ECC>
 AZ_DEVICE bool az_fast_window_ok(const FastK &k, const AzGrav &g, double t_a, double t_b, double dmax = 0.0)
@@ -481,13 +517,19 @@ AZ_DEVICE bool az_fast_window_ok(const FastK &k, const AzGrav &g, double t_a, do
 #ifndef AZ_FAST_PROBE
 #define AZ_FAST_PROBE(name, value)
 #endif
+// ... and AZ_FAST_PROBE_KEPLER(name, value) for what the eccentric tiers' bounds are about: el2 and the corrections d0, d1, d2 of
+// the Kepler iteration (a macro of its own: an emulation that watches the first four names need not know these)
+#ifndef AZ_FAST_PROBE_KEPLER
+#define AZ_FAST_PROBE_KEPLER(name, value)
+#endif
 
 // one near-earth propagation on a uniform grid, inside a window az_fast_window_ok accepted.  Returns true when
 // the eccentric form's Newton iteration left its assumptions for this lane (ECC = true only; the caller must then
 // discard r/v and use az_sgp4_step); the near-circular form always returns false.
 // DELTA (0 none, 1 tight, 2 wide): the grid is quasi-uniform; t is the ACTUAL time of this point and dl = t - (its place on the
 // ideal grid the carried pairs advance along), |dl| <= AZ_DELTA_MAX (tight) / AZ_DELTA_WIDE_MAX (wide).
-// TIER: the body tier az_fast_window_tier assigned to the window (near-circular form; AZ_TIER_GENERAL is valid in all).
+// TIER: the body tier az_fast_window_tier assigned to the window (AZ_TIER_* of the near-circular form, AZ_ETIER_* of the
+// eccentric one; AZ_TIER_GENERAL is valid in every accepted window).
 template <bool VEL, bool ECC = false, int DELTA = 0, int TIER = AZ_TIER_GENERAL, class K = FastK, class RC = RotCoefLit>
 AZ_DEVICE bool az_sgp4_fast_step(const K &k, const AzGrav &g, const RC &rk, double t, FastCarry &st, double r[3],
                                   double v[3], double dl = 0.0)
@@ -518,6 +560,8 @@ AZ_DEVICE bool az_sgp4_fast_step(const K &k, const AzGrav &g, const RC &rk, doub
         else { sW = fma(st.cW, b, st.sW); cW = fma(-st.sW, b, st.cW); }
     }
     const double t2 = t * t;
+    // E1: an eccentric member inside the near-circular Kepler form's (wider) bound; E2: three Newton trips
+    constexpr bool E1 = ECC && TIER == AZ_ETIER_E1, E2 = ECC && TIER == AZ_ETIER_E2;
 
     // secular gravity + drag (Sgp4Batch.zig L121-154)
     const double dm = fma(k.eta(), cA, 1.0);
@@ -531,7 +575,8 @@ AZ_DEVICE bool az_sgp4_fast_step(const K &k, const AzGrav &g, const RC &rk, doub
     if constexpr (DELTA != 0) nl = fma(k.udot(), dl, nl);
     bool bad = false;
     double p, q;
-    if (ECC) az_pq_16th(th, rk, p, q);
+    if (E1) az_fpq_small(th, rk, p, q);                        // ... scaled by em <= 0.01: cos to d^6
+    else if (ECC) az_pq_16th(th, rk, p, q);
     else az_pq_ecc_scaled(th, rk, p, q);                       // M + th and W - th only enter scaled by em < 0.004
     const double smm = fma(cA, p, fma(sA, q, sA));            // sin(M + th)
     const double sw = fma(-cW, p, fma(sW, q, sW));            // (sin,cos)(W - th)
@@ -564,29 +609,73 @@ AZ_DEVICE bool az_sgp4_fast_step(const K &k, const AzGrav &g, const RC &rk, doub
 
     const double el2 = fma(axnl, axnl, aynl * aynl);
     double ecose, esine, ome, inv_ome, betal, inv_omel2, inv_1pb;
-    if (!ECC) {
+    AZ_FAST_PROBE_KEPLER(el2, el2)
+    if (!ECC || E1) {
         // Kepler, near-circular form (see az_kepler_posvel): Newton step from E0 = u, chord step with the
-        // same reciprocal, first-order rotation by the second correction
+        // same reciprocal, first-order rotation by the second correction.  E1 (el <= 0.01, the terms are counted beside
+        // AZ_ETIER_E1): one order more in the first rotation, a second chord step, one term more in two series.
         const double rden = az_rcp1(fma(-s, aynl, fma(-c, axnl, 1.0)));
         const double d0 = fma(axnl, s, -(aynl * c)) * rden;
-        az_fpq_milli(d0, rk, p, q); // |d0| <= el/(1-el) < 0.0041
+        AZ_FAST_PROBE_KEPLER(d0, d0)
+        if (E1) az_pq_ecc_scaled(d0, rk, p, q); // |d0| <= el/(1-el) < 0.0102: sin to d^5
+        else az_fpq_milli(d0, rk, p, q);        // |d0| <= el/(1-el) < 0.0041
         az_rot_apply2(s, c, p, q);
         const double d1 = fma(axnl, s, fma(-aynl, c, -d0)) * rden;
+        AZ_FAST_PROBE_KEPLER(d1, d1)
         {
             const double s1 = fma(c, d1, s);
             c = fma(-s, d1, c);
+            s = s1;
+        }
+        if (E1) {
+            const double d2 = fma(axnl, s, fma(-aynl, c, -(d0 + d1))) * rden;
+            AZ_FAST_PROBE_KEPLER(d2, d2)
+            const double s1 = fma(c, d2, s);
+            c = fma(-s, d2, c);
             s = s1;
         }
         ecose = fma(axnl, c, aynl * s);
         esine = fma(axnl, s, -(aynl * c));
         ome = 1.0 - ecose;
         // 1/(1 - ecose) from the reciprocal of the Newton step (1 - ecose before the two rotations: off by
-        // x ~ el (d0 + d1) <= 1.7e-5 relative): rden (1 + x + x^2), x = 1 - ome rden   (x^3 < 5e-15)
+        // x ~ el (d0 + d1) <= 1.7e-5 relative): rden (1 + x + x^2), x = 1 - ome rden   (x^3 < 5e-15); E1: + x^3
         const double x = fma(-ome, rden, 1.0);
-        inv_ome = fma(rden, fma(x, x, x), rden);
+        inv_ome = fma(rden, E1 ? fma(x, fma(x, x, x), x) : fma(x, x, x), rden);
         betal = fma(el2, fma(el2, -0.125, -0.5), 1.0);    // sqrt(1-x)   (- x^3/16)
         inv_omel2 = el2 + 1.0;                            // 1/(1-x): x^2 < 2.6e-10 relative on the J2 terms (< 1e-3)
+        if (E1) inv_omel2 = fma(el2, inv_omel2, 1.0);     //   E1: + x^2
         inv_1pb = fma(el2, rk(RC_p8), 0.5);               // 1/(1+betal): x^2/16 < 1.6e-11, times esine < 0.004
+    } else if (E2) {
+        // Kepler, el <= 0.1: three Newton trips whose rotation tiers (1/8 rad, 0.0041 rad, first order) follow from the
+        // window's bound on el (beside AZ_ETIER_E2) -- nothing to validate, no hand-over
+        double rden = az_rcp1(fma(-s, aynl, fma(-c, axnl, 1.0)));
+        const double d0 = fma(axnl, s, -(aynl * c)) * rden;
+        AZ_FAST_PROBE_KEPLER(d0, d0)
+        az_pq_med(d0, rk, p, q);
+        az_rot_apply2(s, c, p, q);
+        rden = az_rcp1(fma(-s, aynl, fma(-c, axnl, 1.0)));
+        const double d1 = fma(axnl, s, fma(-aynl, c, -d0)) * rden;
+        AZ_FAST_PROBE_KEPLER(d1, d1)
+        az_fpq_milli(d1, rk, p, q);
+        az_rot_apply2(s, c, p, q);
+        rden = az_rcp1(fma(-s, aynl, fma(-c, axnl, 1.0)));
+        const double d2 = fma(axnl, s, fma(-aynl, c, -(d0 + d1))) * rden;
+        AZ_FAST_PROBE_KEPLER(d2, d2)
+        {
+            const double s1 = fma(c, d2, s);
+            c = fma(-s, d2, c);
+            s = s1;
+        }
+        ecose = fma(axnl, c, aynl * s);
+        esine = fma(axnl, s, -(aynl * c));
+        ome = 1.0 - ecose;
+        // the last trip's reciprocal is 1/(1 - ecose) before the final rotation: off by el*d2, one Newton step
+        inv_ome = fma(rden, fma(-ome, rden, 1.0), rden);
+        const double omel2 = 1.0 - el2;
+        const double rb = az_rsqrt(omel2);
+        betal = omel2 * rb;
+        inv_omel2 = rb * rb;
+        inv_1pb = az_rcp(1.0 + betal);
     } else {
         // Kepler, any near-earth eccentricity (el < ~0.33): five Newton trips on E - aynl cosE + axnl sinE = u
         // carrying eps = E - u and rotating (sinE, cosE) by each correction, with the rotation tier FIXED per

@@ -133,8 +133,12 @@ enum { AZ_ROW_NEAR = 0, AZ_ROW_COPY = 1, AZ_ROW_ZERO = 2 }; // rowmap kinds: slo
 enum { AZ_PLAN_sOc, AZ_PLAN_cOc, AZ_PLAN_sdU, AZ_PLAN_cdU, AZ_PLAN_s1U, AZ_PLAN_c1U, AZ_PLAN_NUM };
 #define AZ_PLAN_OK 1u /* the fast step's validation bounds hold over this window (az_fast_window_ok) */
 #define AZ_PLAN_TC 2u /* the drag phase is expanded about the window centre (tc = tmid), else tc = 0 */
-#define AZ_PLAN_TIER_SHIFT 2 /* bit 2: the window's body tier (fast_step.h AZ_TIER_*; 0 for the eccentric form) */
+#define AZ_PLAN_TIER_SHIFT 2 /* bit 2: the window's body tier (fast_step.h AZ_TIER_*); a slot that carries AZ_PLAN_ECC: bits 2-3, AZ_ETIER_* */
 #define AZ_PLAN_TIER_MASK 1u
+#define AZ_PLAN_ETIER_MASK 3u
+#ifndef AZ_ROWS_ETIERS
+#define AZ_ROWS_ETIERS 1 /* k_rows_fast, eccentric form: one loop body per window tier (0: the five-trip body for every window; 2: E1 and the five-trip body only) */
+#endif
 #define AZ_PLAN_ECC 16u /* the slot runs the eccentric form */
 #define AZ_PLAN_SET 32u /* the entry belongs to a (slot, segment) of the staged grid (the buffer is cleared before the plan is built) */
 
@@ -714,7 +718,8 @@ __global__ void __launch_bounds__(256) k_plan_windows(PlanArgs a)
     az_load_fast(a.el, a.n_pad, s, fl, a.inc, 1, k1);
     az_fast_window(a.el, a.n_pad, s, w_a, w_b, a.step, k1);
     // a class the form cannot take (an eccentric member in the near-circular list) is rejected like a failed bound
-    const int tier = ecc ? az_fast_window_tier<true>(k0, a.g, w_a, w_b, a.delta_max) : az_fast_window_tier<false>(k0, a.g, w_a, w_b, a.delta_max);
+    int tier = ecc ? az_fast_window_tier<true>(k0, a.g, w_a, w_b, a.delta_max) : az_fast_window_tier<false>(k0, a.g, w_a, w_b, a.delta_max);
+    if (ecc && (AZ_ROWS_ETIERS == 0 || (AZ_ROWS_ETIERS == 2 && tier == AZ_ETIER_E2))) tier = min(tier, (int)AZ_TIER_GENERAL); // (built without a body: the plan says what runs)
     bool ok = tier >= 0;
     if (!ecc && AZ_FLAG_ECLASS(fl) != 0) ok = false;
     if (!ecc && a.f32_mixed && !az_fast32p_window_ok(k0, w_a, w_b)) ok = false;
@@ -746,7 +751,7 @@ __device__ __forceinline__ bool az_plan_window(const PropArgs &p, unsigned seg, 
     k0.tmid_ = 0.5 * (w_a + w_b);
     k0.tc_ = (f & AZ_PLAN_TC) ? k0.tmid_ : 0.0;
     k0.sOc_ = w[AZ_PLAN_sOc]; k0.cOc_ = w[AZ_PLAN_cOc]; k0.sdU_ = w[AZ_PLAN_sdU]; k0.cdU_ = w[AZ_PLAN_cdU];
-    if (tier) *tier = (f >> AZ_PLAN_TIER_SHIFT) & AZ_PLAN_TIER_MASK;
+    if (tier) *tier = (f >> AZ_PLAN_TIER_SHIFT) & ((f & AZ_PLAN_ECC) ? AZ_PLAN_ETIER_MASK : AZ_PLAN_TIER_MASK);
     return (f & AZ_PLAN_OK) != 0;
 }
 
@@ -1210,6 +1215,12 @@ __global__ void __launch_bounds__(64, FRAME >= 2 ? 4 : (ECC ? AZ_ROWSF_ECC_WAVES
         };
         // (the tiered bodies: TEME rows of the near-circular form)
         if constexpr (AZ_ROWS_TIERS && !ECC && FRAME == 0) run(std::integral_constant<int, AZ_TIER_EPS>(), tier == AZ_TIER_EPS ? t_hi : t_lo);
+        // (... and of the eccentric form on exact and tight quasi-uniform grids.  Their bounds on el make the Newton predicate
+        // unnecessary: a wave of E1 or E2 leaves its loop at t_hi and files nothing)
+        if constexpr (AZ_ROWS_ETIERS && ECC && FRAME == 0 && DELTA != 2) {
+            run(std::integral_constant<int, AZ_ETIER_E1>(), tier == AZ_ETIER_E1 ? t_hi : t_lo);
+            if constexpr (AZ_ROWS_ETIERS == 1) run(std::integral_constant<int, AZ_ETIER_E2>(), tier == AZ_ETIER_E2 ? t_hi : t_lo);
+        }
         run(std::integral_constant<int, AZ_TIER_GENERAL>(), t_hi);
     }
     if (SINK == AZ_SINK_SCREEN) {

@@ -685,6 +685,16 @@ int32_t azh_last_one_stats(azh_constellation *c, uint32_t *n_segments, uint32_t 
 #define AZH_WINDOW_TIER_REJECTED 3
 #define AZH_WINDOW_TIER_COUNTS 4
 int32_t azh_last_window_tiers(azh_constellation *c, uint32_t counts[AZH_WINDOW_TIER_COUNTS]);
+/* the same plan, the accepted windows of the eccentric form (counts[AZH_WINDOW_TIER_ECC] above) per loop body:
+ * counts[AZH_WINDOW_ECC_E1]: the near-circular Kepler form one notch wider (el <= 0.01), counts[AZH_WINDOW_ECC_E2]: three
+ * Newton trips (el <= 0.1), counts[AZH_WINDOW_ECC_GENERAL]: five trips, validated per step.  The satellite-major TEME row
+ * kernel runs the body of the window's tier on exact and tight quasi-uniform grids; every other fast kernel runs the general
+ * body in all three.  Read back from the plan when asked, like the call above.  Returns an astroz error code. */
+#define AZH_WINDOW_ECC_E1 0
+#define AZH_WINDOW_ECC_E2 1
+#define AZH_WINDOW_ECC_GENERAL 2
+#define AZH_WINDOW_ECC_COUNTS 3
+int32_t azh_last_window_ecc_tiers(azh_constellation *c, uint32_t counts[AZH_WINDOW_ECC_COUNTS]);
 
 #ifdef __cplusplus
 }
